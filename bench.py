@@ -1,6 +1,6 @@
 """Benchmark: Paxos instances decided per second on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4] [--dump-outputs DIR] [--full]
 
 One step = one pxb_run_device call over one batch of fresh synthetic
 instances.  The headline workload is the north star, BASELINE config 4: 2^26
@@ -17,11 +17,24 @@ range (no data-path collective) and the run totals (decided counts,
 violation flags) are summed with one RCCL all-reduce after the timed region.
 `--gpus N` without torchrun spawns the N ranks itself (a child
 torch.distributed.run, started before this process touches a GPU).  Prints
-ONE JSON line on rank 0: the headline first (with its roofline and the CPU
-baseline of the same config), then, on one GPU, `extra`: config 2 (the
-fault-free 2^28-instance batch, the round-1..3 headline), config 4 at 2^23 (the
-per-GPU share at N = 8), configs 3 and 5 at scale, config 5's whole 2^28 sweep
-(totals only), fault-free and faulty log mode, and the wire codec.
+ONE JSON line on rank 0: the headline with its roofline (the committed
+profile's counts over the step time measured now; no run of its own).  A plain
+run does nothing else: set up, warm up, time the K steps, print.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step
+returned to its caller as DIR/<name>.npy (float64, every 32-bit word exact):
+`results` (pxb_result words per instance), `digests` (one log digest per
+acceptor and instance) and `totals` (the run totals over the timed steps).
+Steps of more than DUMP_SAMPLE instances are written as a fixed, seeded sample
+of DUMP_SAMPLE rows (the same rows of both arrays).  The instance ids of a step
+follow from the arguments alone, so two runs with the same arguments write the
+same files.
+
+`--full` adds the CPU baseline of the same config (`--no-cpu` drops it) and, on
+one GPU, `extra` (`--no-extra` drops it): config 2 (the fault-free
+2^28-instance batch, the round-1..3 headline), config 4 at 2^23 (the per-GPU
+share at N = 8), configs 3 and 5 at scale, config 5's whole 2^28 sweep (totals
+only), fault-free and faulty log mode, and the wire codec.
 """
 from __future__ import annotations
 
@@ -64,6 +77,8 @@ PROFILE_ROUNDS = ("r06", "r05", "r04", "r03", "r02")   # the newest committed pr
 BATCHES_PER_STEP = 256       # config-2 batches of 2^20 per timed step (>= 100 ms over 20 steps)
 STEP_STREAMS = 0             # --streams (A/B; --one-stream = 1; 0: by step size, GpuLeg)
 DRY_NORTH_STAR = 1 << 12     # --dry-run stand-in for the headline's 2^26 instances per step
+DUMP_SAMPLE = 1 << 19        # --dump-outputs rows per array (x (4 + 9) float64 words at most: 52 MiB)
+DUMP_SEED = 0x5EEDD0         # of the sample's row choice
 
 
 def parse():
@@ -77,8 +92,12 @@ def parse():
                          "one-GPU --config 5 run takes all 2^28 per step); config 2 is 2^28 per GPU")
     ap.add_argument("--instances", type=int, default=0, help="per GPU per step (default: the config's step size)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline and, on one GPU, the `extra` workloads (off: the headline only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no `extra` workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true", help="CPU ranks (gloo), synthetic work: launcher test only")
     ap.add_argument("--streams", type=int, default=0, help="step streams (default: faulty steps of up to 2^24 instances 4, larger ones 1; fault-free 2)")
     ap.add_argument("--one-stream", action="store_true",
@@ -211,6 +230,46 @@ class GpuLeg:
     def event_ms(self):
         return self.e0.elapsed_time(self.e1)
 
+    def outputs(self, step):
+        """What launch(step, n) handed its caller (after sync()): the step's
+        result and digest buffers as uint32 words, DUMP_SAMPLE seeded rows of
+        them when the step is larger, and the run totals."""
+        import numpy as np
+        k = step % len(self.streams)
+        out = {"totals": self.tot.cpu().numpy()}
+        if self.out[k] is None:
+            return out
+        rows = dump_rows(self.n)
+        if rows is not None:
+            rows = self.torch.from_numpy(rows).to(self.dev)
+        for name, t in (("results", self.out[k]), ("digests", self.dig[k])):
+            t = t[:self.n] if rows is None else t.index_select(0, rows)
+            out[name] = t.cpu().numpy().view(np.uint32)
+        return out
+
+
+def dump_rows(n):
+    """The rows of an n-instance step that --dump-outputs writes: None (all of
+    them) up to DUMP_SAMPLE, else one seeded row from each of DUMP_SAMPLE equal
+    strata of the step (ascending int64, the same for every run)."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return None
+    stride = n // DUMP_SAMPLE
+    pick = np.random.default_rng(DUMP_SEED).integers(0, stride, DUMP_SAMPLE)
+    return np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + pick
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: each array as <path>/<name>.npy (rank r of a job of
+    several: <name>.rank<r>.npy), float64 (exact for every 32-bit word and for
+    the totals, which stay far below 2^53)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        fn = name + (".rank%d" % rank if world > 1 else "") + ".npy"
+        np.save(os.path.join(path, fn), np.asarray(a).astype(np.float64))
+
 
 class DryLeg:
     """--dry-run: the same launcher, barriers, timing and collectives on CPU
@@ -237,6 +296,9 @@ class DryLeg:
 
     def event_ms(self):
         return (self.t[1] - self.t[0]) * 1e3
+
+    def outputs(self, step):
+        return {"totals": self.tot.numpy()}
 
 
 def run_workload(leg, n, steps, warmup, world, warm_n=None):
@@ -507,8 +569,11 @@ def dry_main(args, rank, world):
         dist.init_process_group("gloo")
     total = args.instances or DRY_NORTH_STAR
     n = total // world
-    secs, kms, cnt = run_workload(DryLeg(n, rank, world), n, args.steps, args.warmup, world)
+    leg = DryLeg(n, rank, world)
+    secs, kms, cnt = run_workload(leg, n, args.steps, args.warmup, world)
     assert cnt["instances"] == n * world * args.steps, cnt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, leg.outputs(args.warmup + args.steps - 1), rank, world)
     if rank == 0:
         line = {"metric": "dry-run", "value": cnt["decided"] / secs, "unit": "instances/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": secs / args.steps * 1e3,
@@ -551,10 +616,14 @@ def main():
 
     # the headline: K timed steps of n fresh instances per rank (BASELINE
     # config 4 by default: 2^26 / N per rank, strong scaling)
-    secs, kms, cnt = run_workload(GpuLeg(cfg, n, rank, world, stream, dev), n, args.steps, args.warmup, world)
+    leg = GpuLeg(cfg, n, rank, world, stream, dev)
+    secs, kms, cnt = run_workload(leg, n, args.steps, args.warmup, world)
     total_inst = n * world * args.steps
     assert cnt["instances"] == total_inst, cnt
     assert cnt["decided"] + cnt["undecided"] == total_inst, cnt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, leg.outputs(args.warmup + args.steps - 1), rank, world)
+    del leg          # (its buffers go back to the allocator before any further workload)
     if c == 2:   # closed forms of the fault-free config: every instance decides
         assert cnt["decided"] == total_inst and cnt["canon_bytes"] == 1140 * total_inst, cnt
     value = cnt["decided"] / secs                         # decided instances / s, whole job
@@ -583,9 +652,10 @@ def main():
         "roofline": roofline("config%d" % c, n, kms, cnt["canon_bytes"] / (args.steps * world)),
         "counters": cnt,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    # --full only: the CPU baseline and the other workloads (runs of their own)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
-    if rank == 0 and not args.no_extra and c == 4 and world == 1:
+    if args.full and rank == 0 and not args.no_extra and c == 4 and world == 1:
         extra = {}
         # config 2 (fault-free, 1 proposer, 5 acceptors): 2^28 fresh instances
         # per step, the round 1-3 headline

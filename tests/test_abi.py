@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name)
 
 
-def test_struct_layout_matches_header():
+def test_struct_layout_matches_header(tmp_path):
     src = r'''
 #include <stdio.h>
 #include <stddef.h>
@@ -48,7 +48,7 @@ int main(void) {
          offsetof(pxb_config, step_cap), offsetof(pxb_config, tick_period));
   return 0;
 }'''
-    tmp = "/tmp/pxb_layout"
+    tmp = str(tmp_path / "pxb_layout")
     with open(tmp + ".c", "w") as f:
         f.write(src)
     subprocess.run(["gcc", "-I", os.path.dirname(HEADER), "-o", tmp, tmp + ".c"], check=True)
@@ -203,7 +203,7 @@ def test_wire_device_entry_points_check_their_buffers():
     with pytest.raises(ValueError, match="uint8"):
         pxb._check_bytes("d_bytes", _PosingAsDevice(), 1)
 
-def test_trace_record_layout_matches_bindings():
+def test_trace_record_layout_matches_bindings(tmp_path):
     """pxb_trace_step as the Python mirror (pxb.TRACE_WORDS, word offsets in
     trace_instance) and the Haskell binding (PaxosBatch.traceInstance: 73
     words, digests from word 40, proposers from word 49, 8 words each) read it."""
@@ -216,7 +216,7 @@ int main(void) {
          offsetof(pxb_trace_step, log_digest), offsetof(pxb_trace_step, prop), sizeof(pxb_trace_prop));
   return 0;
 }'''
-    tmp = "/tmp/pxb_trace_layout"
+    tmp = str(tmp_path / "pxb_trace_layout")
     with open(tmp + ".c", "w") as f:
         f.write(src)
     subprocess.run(["gcc", "-I", os.path.dirname(HEADER), "-o", tmp, tmp + ".c"], check=True)

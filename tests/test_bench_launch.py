@@ -61,6 +61,72 @@ def test_bench_rejects_world_mismatch():
     assert out.returncode != 0 and "WORLD_SIZE" in out.stderr
 
 
+def test_bench_dump_outputs_dry(tmp_path):
+    """--dump-outputs on the launcher path: float64 arrays, the same from run to
+    run; a plain line carries neither the CPU baseline nor `extra`."""
+    import numpy as np
+    tots = []
+    for d in ("a", "b"):
+        j = _bench("--dry-run", "--gpus", "1", "--steps", "3", "--warmup", "1", "--instances", "500",
+                   "--dump-outputs", str(tmp_path / d))
+        assert "cpu_baseline" not in j and "extra" not in j and j["ms_per_step"] > 0
+        tots.append(np.load(tmp_path / d / "totals.npy"))
+    assert tots[0].dtype == np.float64 and tots[0].shape == (16,)
+    assert tots[0][13] == 1500 and np.array_equal(tots[0], tots[1])
+
+
+def test_dump_rows():
+    """The rows --dump-outputs keeps of a step: all of a small one, else a fixed
+    sample, one row per stratum, within the 64 MB limit at nine acceptors."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    m = bench.DUMP_SAMPLE
+    assert m * (4 + 9) * 8 <= 64 * 1000 * 1000
+    assert bench.dump_rows(1) is None and bench.dump_rows(m) is None
+    for n in (m + 1, 3 * m + 5, 1 << 26):
+        r = bench.dump_rows(n)
+        assert r.dtype == np.int64 and r.shape == (m,) and np.array_equal(r, bench.dump_rows(n))
+        assert r[0] >= 0 and r[-1] < n and (np.diff(r) > 0).all()
+        assert np.array_equal(r // (n // m), np.arange(m))
+    assert len(set(bench.dump_rows(1 << 26) % 128)) > 1          # (not a fixed stride)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sample", [0, 256])
+def test_dump_outputs_match_oracle(gpu_lib, tmp_path, monkeypatch, sample):
+    """What --dump-outputs writes for a timed run on four step streams is the
+    last step's results and digests (every row, or the sampled rows of a step
+    larger than the sample) and the totals of the timed steps, per the oracle."""
+    import numpy as np
+    import torch
+    import oracle_c
+    import pxb
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "_STREAM_POOL", [])
+    if sample:
+        monkeypatch.setattr(bench, "DUMP_SAMPLE", sample)
+    cfg, n, steps, warmup = pxb.CONFIGS[4], 1000, 6, 1
+    dev = torch.device("cuda", 0)
+    leg = bench.GpuLeg(cfg, n, 0, 1, torch.cuda.Stream(dev), dev)
+    assert len(leg.streams) == 4
+    _, _, cnt = bench.run_workload(leg, n, steps, warmup, 1)
+    last = warmup + steps - 1
+    bench.dump_outputs(str(tmp_path), leg.outputs(last))
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("results", "digests", "totals")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    eres, edig, _, _ = oracle_c.run_cpu(cfg, last * n, n, threads=4)
+    rows = bench.dump_rows(n)
+    assert (rows is None) == (not sample)
+    if rows is not None:
+        eres, edig = eres[rows], edig[rows]
+    assert got["results"].shape == eres.shape and np.array_equal(got["results"], eres)
+    assert got["digests"].shape == edig.shape and np.array_equal(got["digests"], edig)
+    _, _, _, ecnt = oracle_c.run_cpu(cfg, warmup * n, steps * n, threads=4)
+    assert pxb.counters_dict(got["totals"]) == ecnt == cnt
+
+
 def test_step_instances_sized_from_world():
     """Configs 4 and 5 are one batch over the node (64M over 8 GPUs, 256M):
     each rank's share is that batch / world; config 2 is a fixed batch per GPU."""

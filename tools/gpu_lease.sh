@@ -9,8 +9,8 @@
 #   tests                      the full -m gpu suite
 #   tests:<pytest -k expr>     a subset of it
 #   fuzz:<schedules>,<n>[,<seed>[,<kind>+<kind>...]]   tests/fuzz_gpu.py, GPU vs the C oracle
-#   bench                      the default bench line (bench.py, CPU baseline and extra included)
-#   bench:<bench.py args>      e.g. bench:--no-cpu --no-extra --steps 5  (spaces allowed)
+#   bench                      the whole bench line (bench.py --full: CPU baseline and extra included)
+#   bench:<bench.py args>      e.g. bench:--steps 5 (the headline only) or bench:--full --no-cpu  (spaces allowed)
 #   ab:<lib.so>+<lib.so>...    tools/ab_ev.py A/B of library variants (AB_CASES, AB_PASSES from the env)
 #   prof:<config>,<n>,<steps>,<warmup>[,<round>]   tools/profile_set.sh -> profiles/<round>_config<c>
 #   wt:<lib.so>,<config>,<n>   per-wave timelines (tools/ev_wave_times.py, a -DPXB_WAVE_TIMES build)
@@ -42,7 +42,7 @@ for step in "$@"; do
       timeout -k 10 600 python3 -u tests/fuzz_gpu.py $ns $ni $seed ${kinds//+/,} > $O/fuzz_$k.txt 2>&1 || { tail -20 $O/fuzz_$k.txt; exit 1; }
       tail -1 $O/fuzz_$k.txt ;;
     bench)
-      timeout -k 10 600 python3 -u bench.py $arg > $O/bench_$k.json 2> $O/bench_$k.err || { tail -20 $O/bench_$k.err; exit 1; }
+      timeout -k 10 600 python3 -u bench.py ${arg:---full} > $O/bench_$k.json 2> $O/bench_$k.err || { tail -20 $O/bench_$k.err; exit 1; }
       python3 tools/bench_summary.py $O/bench_$k.json ;;
     ab)
       libs=${arg//+/ }
