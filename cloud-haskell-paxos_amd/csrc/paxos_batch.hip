@@ -18,6 +18,7 @@
 #include "paxos_ff1.h"
 #include "paxos_ffp.h"
 #include "paxos_kernel.h"
+#include "sweep_plan.h"
 
 namespace pxb {
 
@@ -284,6 +285,7 @@ struct Hooks {
   int ff1_oversub, ffp_oversub;   // PXB_FF1_OVERSUB / PXB_FFP_OVERSUB (0: FF1_OVERSUB)
   char multi_fail_phase[16];      // PXB_MULTI_FAIL_PHASE / _DEVICE (paxos_multi.cpp)
   int multi_fail_device;
+  uint64_t sweep_chunk;           // PXB_SWEEP_CHUNK (instances per pxb_sweep chunk)
 };
 static Hooks g_hooks;
 static bool g_hooks_read = false;
@@ -561,6 +563,8 @@ static void read_hooks_locked() {
   const char* ph = getenv("PXB_MULTI_FAIL_PHASE");
   if (ph) snprintf(h.multi_fail_phase, sizeof(h.multi_fail_phase), "%s", ph);
   h.multi_fail_device = num("PXB_MULTI_FAIL_DEVICE", -1);
+  const char* sc = getenv("PXB_SWEEP_CHUNK");
+  h.sweep_chunk = sc ? sweep_clamp_chunk(atoll(sc)) : SWEEP_CHUNK_DEFAULT;
   g_hooks = h;
   g_hooks_read = true;
 }
@@ -1093,6 +1097,65 @@ int pxb_run(const pxb_config* cfg, pxb_result* out, uint32_t* log_digest, pxb_ac
   if (d_dig) (void)hipFree(d_dig);
   if (d_acc) (void)hipFree(d_acc);
   if (d_tot) (void)hipFree(d_tot);
+  return rc;
+}
+
+extern "C" int pxb_query_validate(const pxb_query* q, const void* ids, uint64_t capacity, const void* n_matches,
+                                  const void* hist_steps, const void* hist_rounds);   // paxos_query.hip
+
+// Chunk by chunk (sweep_plan.h): run into the one result buffer, then query it
+// on the same stream with the running cursor.  The query is a vanishing part
+// of a chunk's time, so nothing overlaps; the device holds one chunk of
+// results, the match list and the bins, whatever n_instances is.
+int pxb_sweep(const pxb_config* cfg, const pxb_query* q, uint64_t* ids, pxb_result* matched, uint64_t capacity,
+              uint64_t* n_matches, int64_t* hist_steps, int64_t* hist_rounds, pxb_counters* totals) {
+  int rc = validate(cfg);
+  if (rc) return rc;
+  if ((rc = pxb_query_validate(q, ids, capacity, n_matches, hist_steps, hist_rounds))) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
+  const uint64_t n = cfg->n_instances, chunk = hooks().sweep_chunk;
+  const uint64_t cap = std::min(capacity, n);            // (no more matches than instances)
+  const size_t bs = q->n_bins_steps * sizeof(int64_t), br = q->n_bins_rounds * sizeof(int64_t);
+  pxb_result *d_res = nullptr, *d_matched = nullptr;
+  uint64_t *d_ids = nullptr, *d_cur = nullptr;
+  int64_t *d_hs = nullptr, *d_hr = nullptr, *d_tot = nullptr;
+  hipError_t e = hipSuccess;
+  do {
+    if (n && (e = hipMalloc(&d_res, std::min(n, chunk) * sizeof(pxb_result))) != hipSuccess) break;
+    if (cap && (e = hipMalloc(&d_ids, cap * sizeof(uint64_t))) != hipSuccess) break;
+    if (cap && matched && (e = hipMalloc(&d_matched, cap * sizeof(pxb_result))) != hipSuccess) break;
+    if (bs && (e = hipMalloc(&d_hs, bs)) != hipSuccess) break;
+    if (br && (e = hipMalloc(&d_hr, br)) != hipSuccess) break;
+    if ((e = hipMalloc(&d_cur, sizeof(uint64_t))) != hipSuccess) break;
+    if ((e = hipMalloc(&d_tot, PXB_NCOUNTERS * sizeof(int64_t))) != hipSuccess) break;
+    if ((e = hipMemset(d_cur, 0, sizeof(uint64_t))) != hipSuccess) break;
+    if ((e = hipMemset(d_tot, 0, PXB_NCOUNTERS * sizeof(int64_t))) != hipSuccess) break;
+    if (bs && (e = hipMemset(d_hs, 0, bs)) != hipSuccess) break;
+    if (br && (e = hipMemset(d_hr, 0, br)) != hipSuccess) break;
+    pxb_config c = *cfg;
+    for (uint64_t k = 0, nk = sweep_n_chunks(n, chunk); k < nk && rc == PXB_OK; ++k) {
+      const SweepChunk ch = sweep_chunk_at(cfg->first_instance, n, chunk, k);
+      c.first_instance = ch.first;
+      c.n_instances = ch.count;
+      if ((rc = pxb_run_device(&c, d_res, nullptr, nullptr, d_tot, nullptr)) != PXB_OK) break;
+      rc = pxb_query_device(d_res, ch.first, ch.count, q, d_ids, d_matched, cap, d_cur, d_hs, d_hr, nullptr);
+    }
+    // (also after a failed chunk: nothing is freed under queued work)
+    if ((e = hipDeviceSynchronize()) != hipSuccess || rc != PXB_OK) break;
+    if ((e = hipMemcpy(n_matches, d_cur, sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
+    const uint64_t nw = std::min(*n_matches, cap);
+    if (nw && (e = hipMemcpy(ids, d_ids, nw * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
+    if (nw && matched && (e = hipMemcpy(matched, d_matched, nw * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess)
+      break;
+    if (bs && (e = hipMemcpy(hist_steps, d_hs, bs, hipMemcpyDeviceToHost)) != hipSuccess) break;
+    if (br && (e = hipMemcpy(hist_rounds, d_hr, br, hipMemcpyDeviceToHost)) != hipSuccess) break;
+    if (totals && (e = hipMemcpy(totals->c, d_tot, PXB_NCOUNTERS * sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
+      break;
+  } while (0);
+  if (e != hipSuccess) rc = hip_fail(e);
+  for (void* p : {(void*)d_res, (void*)d_ids, (void*)d_matched, (void*)d_hs, (void*)d_hr, (void*)d_cur, (void*)d_tot})
+    if (p) (void)hipFree(p);
   return rc;
 }
 

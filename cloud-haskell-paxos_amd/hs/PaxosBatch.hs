@@ -37,6 +37,11 @@ module PaxosBatch
   , ProposerState (..)
   , TraceStep (..)
   , traceInstance
+    -- * Result queries (which instances to trace, without the results on the host)
+  , Query (..)
+  , FlagMode (..)
+  , everything
+  , sweep
   ) where
 
 import           Common                (Command, Proposal, Ticket (..))
@@ -49,7 +54,7 @@ import           Data.Word             (Word32, Word64)
 import           Foreign.C.String      (CString, peekCString)
 import           Foreign.C.Types       (CInt (..))
 import           Foreign.ForeignPtr    (mallocForeignPtrArray, withForeignPtr)
-import           Foreign.Marshal.Array (advancePtr, allocaArray, peekArray)
+import           Foreign.Marshal.Array (advancePtr, allocaArray, peekArray, withArray)
 import           Foreign.Marshal.Utils (with)
 import           Foreign.Ptr           (Ptr, nullPtr)
 import           Foreign.Storable      (Storable (..))
@@ -148,6 +153,10 @@ foreign import ccall safe "pxb_handoff_counts"
   c_pxb_handoff_counts :: CInt -> Ptr Word64 -> CInt -> IO CInt
 foreign import ccall safe "pxb_trace_instance"
   c_pxb_trace_instance :: Ptr BatchConfig -> Word64 -> Ptr Word32 -> Word32 -> Ptr Word32 -> Ptr Word32 -> IO CInt
+
+foreign import ccall safe "pxb_sweep"
+  c_pxb_sweep :: Ptr BatchConfig -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64
+              -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> IO CInt
 
 -- | The ABI this module was written against (include/paxos_batch.h).
 expectedAbi :: Int
@@ -305,3 +314,62 @@ traceInstance cfg i maxRecords = do
                                    (cmd (at (b + 6))) (at (b + 7) /= 0)
       in TraceStep (fromIntegral (at 0)) (if at 1 == 0xFFFFFFFF then Nothing else Just (fromIntegral (at 1)))
                    (map acc [0 .. nA - 1]) (map pro [0 .. nP - 1])
+
+-- | pxb_query.flag_mode: how (flags .&. mask) is tested.
+data FlagMode = AnyOf | AllOf | NoneOf
+  deriving (Show, Eq, Enum)
+
+-- | pxb_query (32 bytes): the flag test, inclusive ranges on an instance's
+-- steps and rounds, and the bins of the two histograms (0: none, at most 8194;
+-- values beyond the last bin are counted in it).
+data Query = Query
+  { qFlags      :: [Flag]
+  , qMode       :: !FlagMode
+  , qSteps      :: !(Word32, Word32)
+  , qRounds     :: !(Word32, Word32)
+  , qStepsBins  :: !Int
+  , qRoundsBins :: !Int
+  } deriving (Show)
+
+-- | Matches every instance; no histograms.
+everything :: Query
+everything = Query [] NoneOf (0, maxBound) (0, maxBound) 0 0
+
+-- | pxb_sweep: run the batch chunk by chunk on the current GPU and keep only
+-- what the query asks for: the global ids and outcomes of the first @capacity@
+-- matching instances (ascending), the number of matches, the two histograms
+-- and the run totals.  Feed an id to 'traceInstance' to see what happened.
+-- (additive to ABI 5: a library without the symbol fails to link)
+sweep :: BatchConfig -> Query -> Int
+      -> IO (Either String ([(Word64, Outcome)], Word64, [Int64], [Int64], Totals))
+sweep cfg q capacity = do
+  let mask = sum [2 ^ fromEnum fl | fl <- qFlags q] :: Word32
+      qw = [ mask, fromIntegral (fromEnum (qMode q)), fst (qSteps q), snd (qSteps q)
+           , fst (qRounds q), snd (qRounds q), fromIntegral (qStepsBins q), fromIntegral (qRoundsBins q) ]
+      orNull k p = if k == 0 then nullPtr else p
+  fids <- mallocForeignPtrArray (max 1 capacity)
+  fres <- mallocForeignPtrArray (max 1 (4 * capacity))
+  with cfg $ \pc ->
+    withArray qw $ \pq ->
+      withForeignPtr fids $ \pids ->
+        withForeignPtr fres $ \pres ->
+          allocaArray 1 $ \pn ->
+            allocaArray (max 1 (qStepsBins q)) $ \phs ->
+              allocaArray (max 1 (qRoundsBins q)) $ \phr ->
+                allocaArray 16 $ \ptot -> do
+                  rc <- c_pxb_sweep pc pq (orNull capacity pids) (orNull capacity pres) (fromIntegral capacity) pn
+                                    (orNull (qStepsBins q) phs) (orNull (qRoundsBins q) phr) ptot
+                  if rc /= 0
+                    then Left <$> (c_pxb_strerror rc >>= peekCString)
+                    else do
+                      [n] <- peekArray 1 pn
+                      let k = fromIntegral (min n (fromIntegral capacity)) :: Int
+                      ids <- peekArray k pids
+                      outs <- forM [0 .. k - 1] $ \i -> do
+                        [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                        pure (decode v t r f)
+                      hs <- peekArray (qStepsBins q) phs
+                      hr <- peekArray (qRoundsBins q) phr
+                      tot <- peekArray 16 ptot
+                      let [d, u, s, p, dv, sc, rd, ms] = take 8 tot
+                      pure (Right (zip ids outs, n, hs, hr, Totals d u s p dv sc rd ms (tot !! 14)))

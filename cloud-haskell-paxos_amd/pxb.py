@@ -85,8 +85,40 @@ class pxb_proposer_rec(C.Structure):
                 ("client_id", C.c_uint32)]
 
 
+class pxb_query(C.Structure):
+    _fields_ = [("flag_mask", C.c_uint32), ("flag_mode", C.c_uint32),
+                ("steps_min", C.c_uint32), ("steps_max", C.c_uint32),
+                ("rounds_min", C.c_uint32), ("rounds_max", C.c_uint32),
+                ("n_bins_steps", C.c_uint32), ("n_bins_rounds", C.c_uint32)]
+
+
 assert C.sizeof(pxb_config) == 72 and C.sizeof(pxb_result) == 16
 assert C.sizeof(pxb_acceptor_rec) == 16 and C.sizeof(pxb_msg) == 16
+assert C.sizeof(pxb_query) == 32
+
+# pxb_query.flag_mode / histogram bound
+Q_ANY, Q_ALL, Q_NONE = 0, 1, 2
+HIST_MAX_BINS = 8194
+U32_MAX = 0xFFFFFFFF
+
+
+@dataclass
+class Query:
+    """pxb_query: the flag test (flags & flag_mask against Q_ANY / Q_ALL /
+    Q_NONE), inclusive ranges on the steps and the rounds, and the number of
+    bins of the two histograms (0 = none).  The default matches everything."""
+    flag_mask: int = 0
+    flag_mode: int = Q_NONE
+    steps_min: int = 0
+    steps_max: int = U32_MAX
+    rounds_min: int = 0
+    rounds_max: int = U32_MAX
+    n_bins_steps: int = 0
+    n_bins_rounds: int = 0
+
+    def to_c(self) -> pxb_query:
+        return pxb_query(self.flag_mask, self.flag_mode, self.steps_min, self.steps_max,
+                         self.rounds_min, self.rounds_max, self.n_bins_steps, self.n_bins_rounds)
 
 # ---- Common.hs vocabulary ------------------------------------------------
 
@@ -205,7 +237,9 @@ def load(path: str = LIB_PATH):
                        ("pxb_wire_encode_host", [vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
                        ("pxb_wire_decode_host", [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp]),
                        ("pxb_init", [C.c_int]), ("pxb_shutdown", []),
-                       ("pxb_trace_instance", [vp, C.c_uint64, vp, C.c_uint32, vp, vp])):
+                       ("pxb_trace_instance", [vp, C.c_uint64, vp, C.c_uint32, vp, vp]),
+                       ("pxb_query_device", [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_sweep", [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
     lib.pxb_stream_release.argtypes = [C.c_int, vp]
@@ -310,6 +344,61 @@ def run_device(cfg: Config, first_instance: int, n_instances: int, d_results=Non
     s = C.c_void_p(stream) if stream else None
     check(lib.pxb_run_device(C.byref(c), _ptr(d_results), _ptr(d_digests), _ptr(d_acceptors),
                              _ptr(d_totals), s))
+
+
+def query_device(d_results, first_instance: int, count: int, query: Query, d_n_matches, d_ids=None,
+                 d_matched=None, capacity: int = 0, d_hist_steps=None, d_hist_rounds=None, stream=None):
+    """pxb_query_device on torch tensors, asynchronous on `stream`: applies
+    `query` to d_results[:count] (int32 (count, 4), the results of instances
+    first_instance..).  Matching global ids go to d_ids (int64, `capacity`
+    entries) and their records to d_matched (int32 (capacity, 4), optional) in
+    ascending order from the cursor d_n_matches (int64, one entry), which then
+    has the call's full match count added; the histograms (int64, n_bins
+    entries) are added to.  Sizes and dtypes are checked here: the C ABI takes
+    raw pointers."""
+    if d_n_matches is None:
+        raise ValueError("d_n_matches is required")
+    if count and d_results is None:
+        raise ValueError("d_results is required")
+    if capacity and d_ids is None:
+        raise ValueError("d_ids is required when capacity > 0")
+    if (query.n_bins_steps and d_hist_steps is None) or (query.n_bins_rounds and d_hist_rounds is None):
+        raise ValueError("a histogram buffer is required when its n_bins > 0")
+    _check_buf("d_results", d_results, 4 * count, 4)
+    _check_buf("d_n_matches", d_n_matches, 1, 8)
+    _check_buf("d_ids", d_ids, capacity, 8)
+    _check_buf("d_matched", d_matched, 4 * capacity, 4)
+    _check_buf("d_hist_steps", d_hist_steps, query.n_bins_steps, 8)
+    _check_buf("d_hist_rounds", d_hist_rounds, query.n_bins_rounds, 8)
+    lib = load()
+    q = query.to_c()
+    s = C.c_void_p(stream) if stream else None
+    check(lib.pxb_query_device(_ptr(d_results), first_instance, count, C.byref(q), _ptr(d_ids), _ptr(d_matched),
+                               capacity, _ptr(d_n_matches), _ptr(d_hist_steps), _ptr(d_hist_rounds), s))
+
+
+def sweep(cfg: Config, first_instance: int, n_instances: int, query: Query, capacity: int):
+    """pxb_sweep: run n_instances instances chunk by chunk and query every
+    chunk on the device; only the match list, the bins and the totals come
+    back.  Returns (ids uint64 (k,), matched uint32 (k, 4), n_matches,
+    hist_steps int64 (n_bins_steps,), hist_rounds int64 (n_bins_rounds,),
+    counters dict) with k = min(n_matches, capacity): the k smallest matching
+    ids; n_matches is the full count."""
+    import numpy as np
+    lib = load()
+    ids = np.zeros(capacity, dtype=np.uint64)
+    matched = np.zeros((capacity, 4), dtype=np.uint32)
+    hs = np.zeros(query.n_bins_steps, dtype=np.int64)
+    hr = np.zeros(query.n_bins_rounds, dtype=np.int64)
+    nm = C.c_uint64(0)
+    tot = pxb_counters()
+    c = cfg.to_c(first_instance, n_instances)
+    q = query.to_c()
+    check(lib.pxb_sweep(C.byref(c), C.byref(q), _ptr(ids) if capacity else None, _ptr(matched) if capacity else None,
+                        capacity, C.byref(nm), _ptr(hs) if len(hs) else None, _ptr(hr) if len(hr) else None,
+                        C.cast(C.byref(tot), C.c_void_p)))
+    k = min(nm.value, capacity)
+    return ids[:k], matched[:k], nm.value, hs, hr, counters_dict(tot.c)
 
 
 def counters_dict(c) -> dict:

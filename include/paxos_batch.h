@@ -366,6 +366,75 @@ int pxb_handoff_counts(int dev, uint64_t* out2, int reset);
  * never calls getenv.  Not for production use; unset, nothing changes.       */
 void pxb_reload_hooks(void);
 
+/* ---- result queries (additive to ABI 5: PXB_ABI_VERSION is unchanged, callers
+ * detect these two entry points by symbol) -----------------------------------
+ * Which instances to hand to pxb_trace_instance, and the distributions the run
+ * totals only sum, without copying 16 B per instance to the host.             */
+#define PXB_Q_ANY   0u   /* (flags & flag_mask) != 0          */
+#define PXB_Q_ALL   1u   /* (flags & flag_mask) == flag_mask  */
+#define PXB_Q_NONE  2u   /* (flags & flag_mask) == 0          */
+#define PXB_HIST_MAX_BINS 8194   /* steps 0..PXB_MAX_STEP_CAP exact, plus one overflow bin */
+
+/* An instance matches when its flags pass the flag test and its steps and
+ * rounds both lie in their inclusive ranges (min > max: nothing matches). */
+typedef struct pxb_query {      /* 32 B */
+  uint32_t flag_mask;           /* PXB_F_* bits only (<= 0xFF)                       */
+  uint32_t flag_mode;           /* PXB_Q_*                                           */
+  uint32_t steps_min, steps_max;    /* inclusive, on PXB_RESULT_STEPS(flags)         */
+  uint32_t rounds_min, rounds_max;  /* inclusive, on pxb_result.rounds               */
+  uint32_t n_bins_steps;        /* 0 = no histogram, else 1..PXB_HIST_MAX_BINS       */
+  uint32_t n_bins_rounds;
+} pxb_query;
+
+/* pxb_query_device: DEVICE buffers, asynchronous on `stream`.  Applies q to
+ * d_results[0..count), the results of instances first_instance.. (as
+ * pxb_run_device leaves them).  Matches are written in ascending instance
+ * order: d_ids[k] = first_instance + index (global ids), d_matched[k]
+ * (nullable) the matching record.  *d_n_matches is read as the write cursor
+ * and then has the call's full match count added to it, so successive calls on
+ * successive chunks append to one list.  Matches whose position is at or past
+ * `capacity` are counted but never written, and nothing past `capacity`
+ * entries is touched.  The histograms count matching instances only:
+ * hist[min(value, n_bins - 1)] += 1, added to what is already there, as
+ * d_totals is ({flag_mask = 0, PXB_Q_NONE} with full ranges: everything).
+ * All integers: results are bit-reproducible.
+ * d_ids may be NULL only when capacity == 0, a histogram pointer only when its
+ * n_bins is 0; d_n_matches is required; any count up to 2^40, 0 included.
+ * PXB_E_INVAL, before any device call, for a null q, flag_mode > 2,
+ * flag_mask > 0xFF, n_bins above PXB_HIST_MAX_BINS or a pointer rule broken.
+ * Three passes, and no kernel of the library's that waits for another block:
+ * per-tile match counts fused with the histograms, a scan of the tile counts
+ * (hipCUB's, as in the wire codec), a scatter that re-reads the tiles that hold
+ * matches.  d_results and d_matched are 16-byte aligned (the records move as
+ * 16-byte words).  Each call takes its tile counts and offsets
+ * (12 B per 1024 results) from the per-device stream-ordered pool of the wire
+ * codec, on its own stream: calls on different streams share nothing.         */
+int pxb_query_device(const pxb_result* d_results, uint64_t first_instance, uint64_t count,
+                     const pxb_query* q,
+                     uint64_t* d_ids, pxb_result* d_matched, uint64_t capacity,
+                     uint64_t* d_n_matches,
+                     int64_t* d_hist_steps, int64_t* d_hist_rounds, void* stream);
+
+/* pxb_sweep: HOST buffers, blocking, on the current device.  Runs
+ * cfg->n_instances instances in chunks of at most 2^24 (one pxb_run_device
+ * each, no digests or acceptor records, into one reused result buffer) and
+ * queries each chunk on the device with a running cursor, so only the match
+ * list, the bins and the totals cross to the host.  *n_matches (the full match
+ * count) and the histograms (n_bins entries each) are OVERWRITTEN; ids and
+ * matched (nullable) hold `capacity` entries: the smallest matching ids;
+ * totals (nullable) are pxb_run's.  The answer is exactly the query applied on
+ * the host to pxb_run's results.
+ * Device memory, whatever n_instances is: one chunk of results (16 B x
+ * min(n_instances, 2^24) = 256 MiB at most, + 12 B per 1024 of them while a
+ * query runs) + min(capacity, n_instances) x 24 B (16 without `matched`) +
+ * 8 B x the bins + the run's own per-device scratch.
+ * Validation as pxb_query_device's and pxb_run's; PXB_E_NODEV without a GPU.
+ * (PXB_SWEEP_CHUNK, a test hook read like the others, clamped to
+ * [1, 2^30 - 1], sets the chunk size.)                                        */
+int pxb_sweep(const pxb_config* cfg, const pxb_query* q,
+              uint64_t* ids, pxb_result* matched, uint64_t capacity, uint64_t* n_matches,
+              int64_t* hist_steps, int64_t* hist_rounds, pxb_counters* totals);
+
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
 int         pxb_last_hip_error(void);
