@@ -7,55 +7,10 @@
 
 #include "../../include/paxos_batch.h"
 #include "paxos_ev_kernel.h"
+#include "paxos_trace_core.h"   // trace_record, trace_config_ok
 
 namespace pxb {
 namespace ev {
-
-template <class Lane>
-__device__ void trace_record(const Lane& L, uint32_t step, pxb_trace_step* r) {
-  constexpr int PM = Lane::S::PM, N = Lane::S::N;
-  constexpr bool LG = Lane::S::LG;
-  constexpr bool EARLY = Lane::kEarly;
-  r->step = step;
-  // (production variant: copies of a broadcast still to send are not on the
-  // links yet, so the count is not the oracle's end-of-step one)
-  r->in_flight = (EARLY && L.pq_len != 0u) ? PXB_TRACE_IN_FLIGHT_UNKNOWN : L.links_in_flight();
-  r->n_acceptors = N;
-  r->n_proposers = L.P;
-  for (int a = 0; a < PXB_MAX_ACCEPTORS; ++a) {
-    uint32_t rec[4] = {0, 0, 0, 0};
-    if (a < N) L.record_of(a, rec);
-    r->acc[a].t_max = (int32_t)rec[0];
-    r->acc[a].t_store = (int32_t)rec[1];
-    r->acc[a].val = rec[2];
-    r->acc[a].meta = rec[3];
-    r->log_digest[a] = a < N ? L.digest_of(a) : 0u;
-  }
-  for (int p = 0; p < PXB_MAX_PROPOSERS; ++p) {
-    pxb_trace_prop q = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (p < PM && (uint32_t)p < L.P) {
-      q.ticket = (int32_t)L.p_ticket(p);
-      q.acks = L.p_acks(p);
-      q.state = L.p_state(p);
-      q.mr_t = (int32_t)L.p_mr_t(p);
-      q.pending = L.p_pending(p);
-      if constexpr (LG) {
-        // log mode: 14-bit commands id [13:12] | t [11:0] (mr_v | r2_v << 14 in
-        // pw1), the proposer's own command c<p+1>.<t> with t in pw2 (0: Nothing)
-        const uint32_t mv = L.pw1[p] & 0x3FFFu, rv = (L.pw1[p] >> 14) & 0x3FFFu, ct = L.pw2[p];
-        q.cmd = ct ? (((uint32_t)p + 1u) << 24) | ct : 0u;
-        q.mr_v = mv ? Lane::code_of(mv) : 0u;
-        q.r2_v = rv ? Lane::code_of(rv) : 0u;
-      } else {
-        const uint32_t code = 1u;   // every command is c<id>.1 (docs/SEMANTICS.md §2)
-        q.cmd = L.p_cmd(p) ? ((L.p_cmd(p) << 24) | code) : 0u;
-        q.mr_v = L.p_mr_v(p) ? ((L.p_mr_v(p) << 24) | code) : 0u;
-        q.r2_v = L.p_r2_v(p) ? ((L.p_r2_v(p) << 24) | code) : 0u;
-      }
-    }
-    r->prop[p] = q;
-  }
-}
 
 // one wave, lane 0 runs the instance; status[0] = records written,
 // status[1] = 1 bailed / 2 out of records.  EARLY = false (the default trace):
@@ -86,6 +41,15 @@ __global__ __launch_bounds__(64) void paxos_trace_kernel(EvParams p, uint32_t gi
       break;
     }
     if (done || L.s != s0) {
+      // an instance that ends at the step cap ends from its last visited step,
+      // s0, and its final step is step_cap - 1: both are recorded (the same state)
+      if (trace_cap_jump(done, o, L.s, s0)) {
+        if (n >= max) {
+          status[1] = 2u;
+          break;
+        }
+        trace_record(L, (uint32_t)s0, out + n++);
+      }
       const uint32_t step = (uint32_t)(done ? L.s : s0);
       // (production variant: an instance whose carried step held only lost
       // copies ends at the step before it, already recorded: rewrite that record)
@@ -146,15 +110,10 @@ extern "C" int pxb_trace_instance(const pxb_config* cfg, uint64_t instance, pxb_
                                   uint32_t* n_records, pxb_result* result) {
   using namespace pxb::ev;
   if (!cfg || !out || !n_records || max_records == 0) return PXB_E_INVAL;
-  if (cfg->n_proposers < 1 || cfg->n_proposers > PXB_MAX_PROPOSERS || cfg->n_acceptors < PXB_MIN_ACCEPTORS ||
-      cfg->n_acceptors > PXB_MAX_ACCEPTORS || cfg->delay_max < 1 || cfg->delay_max > PXB_MAX_DELAY ||
-      cfg->step_cap < 1 || !eligible(cfg))
-    return PXB_E_INVAL;
   // log mode (n_ticks > 1, ABI 5): the batch kernels' log-mode shape (its
   // ticker, 14-bit commands, Execute-driven logs); eligible() holds its delays
   // to the 8-step wheel
-  if (cfg->n_ticks > PXB_MAX_TICKS || (cfg->n_ticks > 1 && (cfg->tick_period < 1 || cfg->tick_period > PXB_MAX_STEP_CAP)))
-    return PXB_E_INVAL;
+  if (!trace_config_ok(cfg)) return PXB_E_INVAL;
   const bool lg = cfg->n_ticks > 1;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;

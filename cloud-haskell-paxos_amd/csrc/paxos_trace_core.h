@@ -1,0 +1,183 @@
+// paxos_trace_core.h — what the trace kernels share, as plain C++ over the
+// per-lane state machine (paxos_ev.h): the record of one step (trace_record,
+// used by pxb_trace_instance and pxb_trace_batch) and the per-lane core of the
+// batched trace (TraceLane: one instance, one iteration at a time, counting or
+// writing the records a selection keeps).  The host unit test
+// (tests/native/trace_host.cpp) compiles the same code over a host accessor.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/paxos_batch.h"
+#include "paxos_ev.h"
+
+namespace pxb {
+namespace ev {
+
+template <class Lane>
+__host__ __device__ void trace_record(const Lane& L, uint32_t step, pxb_trace_step* r) {
+  constexpr int PM = Lane::S::PM, N = Lane::S::N;
+  constexpr bool LG = Lane::S::LG;
+  constexpr bool EARLY = Lane::kEarly;
+  r->step = step;
+  // (production variant: copies of a broadcast still to send are not on the
+  // links yet, so the count is not the oracle's end-of-step one)
+  r->in_flight = (EARLY && L.pq_len != 0u) ? PXB_TRACE_IN_FLIGHT_UNKNOWN : L.links_in_flight();
+  r->n_acceptors = N;
+  r->n_proposers = L.P;
+  for (int a = 0; a < PXB_MAX_ACCEPTORS; ++a) {
+    uint32_t rec[4] = {0, 0, 0, 0};
+    if (a < N) L.record_of(a, rec);
+    r->acc[a].t_max = (int32_t)rec[0];
+    r->acc[a].t_store = (int32_t)rec[1];
+    r->acc[a].val = rec[2];
+    r->acc[a].meta = rec[3];
+    r->log_digest[a] = a < N ? L.digest_of(a) : 0u;
+  }
+  for (int p = 0; p < PXB_MAX_PROPOSERS; ++p) {
+    pxb_trace_prop q = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (p < PM && (uint32_t)p < L.P) {
+      q.ticket = (int32_t)L.p_ticket(p);
+      q.acks = L.p_acks(p);
+      q.state = L.p_state(p);
+      q.mr_t = (int32_t)L.p_mr_t(p);
+      q.pending = L.p_pending(p);
+      if constexpr (LG) {
+        // log mode: 14-bit commands id [13:12] | t [11:0] (mr_v | r2_v << 14 in
+        // pw1), the proposer's own command c<p+1>.<t> with t in pw2 (0: Nothing)
+        const uint32_t mv = L.pw1[p] & 0x3FFFu, rv = (L.pw1[p] >> 14) & 0x3FFFu, ct = L.pw2[p];
+        q.cmd = ct ? (((uint32_t)p + 1u) << 24) | ct : 0u;
+        q.mr_v = mv ? Lane::code_of(mv) : 0u;
+        q.r2_v = rv ? Lane::code_of(rv) : 0u;
+      } else {
+        const uint32_t code = 1u;   // every command is c<id>.1 (docs/SEMANTICS.md §2)
+        q.cmd = L.p_cmd(p) ? ((L.p_cmd(p) << 24) | code) : 0u;
+        q.mr_v = L.p_mr_v(p) ? ((L.p_mr_v(p) << 24) | code) : 0u;
+        q.r2_v = L.p_r2_v(p) ? ((L.p_r2_v(p) << 24) | code) : 0u;
+      }
+    }
+    r->prop[p] = q;
+  }
+}
+
+// the records a selection keeps of `cnt` in-window ones: all, or the last `tail`
+__host__ __device__ inline uint32_t trace_kept(uint32_t cnt, uint32_t tail) {
+  return (tail != 0u && cnt > tail) ? tail : cnt;
+}
+
+// true when an iteration ended the instance at the step cap from a visited
+// step s0 below its final step (s = step_cap - 1): the next message fell due
+// past the cap.  The trace then records s0 and the final step, so that the step
+// in which the final state was reached is told (o is set only when done).
+__host__ __device__ __forceinline__ bool trace_cap_jump(bool done, const EvOut& o, int32_t s, int32_t s0) {
+  return done && (o.flags & PXB_F_STEP_CAP) != 0u && s > s0;
+}
+
+// One instance of the batched trace on one lane.  The caller runs
+//   begin_count / begin_write;  L.init(...);  while (T.iter(L, p)) {}
+// (on the device with the wave's ballot as the loop's back edge).
+//
+// Count pass: runs the instance to its end; n = the visited steps inside
+// [smin, smax], status and the result are the instance's.
+// Write pass (the state machine is deterministic: the same steps again):
+// in-window record j goes to out[j - skip] when j >= skip and j - skip < room
+// (skip: the in-window records a tail drops; room: the caller's capacity left
+// from this instance's offset), and the lane stops once no later record can be
+// kept.
+//
+// The loop is paxos_trace_kernel's: a step is visited when the instance ended
+// in it or the lane moved on to another; the production variant (EARLY) may
+// record the step it ends in a second time (a carried step that held only lost
+// copies ends at the step before it): that record is rewritten, counted once.
+template <class Lane>
+struct TraceLane {
+  static constexpr bool EARLY = Lane::kEarly;
+  static constexpr uint32_t NO_STEP = 0xFFFFFFFFu;   // (steps are < 4095)
+  uint32_t smin, smax;
+  uint32_t n;                       // in-window records so far
+  uint32_t last_step;               // the last visited step (in the window or not)
+  pxb_trace_step* out;              // write pass: this instance's first kept record (count pass: null)
+  uint32_t skip, total;             // write pass: records the tail drops, the count pass's n
+  uint64_t room;
+  uint32_t status;
+  uint32_t res[4];
+
+  __host__ __device__ void begin_count(uint32_t step_min, uint32_t step_max) {
+    smin = step_min;
+    smax = step_max;
+    n = 0u;
+    last_step = NO_STEP;
+    out = nullptr;
+    skip = total = 0u;
+    room = 0ull;
+    status = PXB_TRACE_OK;
+    res[0] = res[1] = res[2] = res[3] = 0u;
+  }
+  // cnt: the count pass's n of this instance (> 0), tail: the selection's, o:
+  // where its first kept record goes, room_: records that fit from there (> 0)
+  __host__ __device__ void begin_write(uint32_t step_min, uint32_t step_max, uint32_t cnt, uint32_t tail,
+                                       pxb_trace_step* o, uint64_t room_) {
+    begin_count(step_min, step_max);
+    out = o;
+    total = cnt;
+    skip = cnt - trace_kept(cnt, tail);
+    room = room_;
+  }
+
+  // a visited step's record: counted, and written where the selection keeps it;
+  // false once the lane has nothing left to do (write pass only)
+  __host__ __device__ __forceinline__ bool visit(const Lane& L, uint32_t step, bool again) {
+    // write pass: a new record that is past the window, the count or the room: nothing later is kept
+    if (out && !again && (n == total || step > smax || (n >= skip && (uint64_t)(n - skip) >= room))) return false;
+    last_step = step;
+    if (step >= smin && step <= smax) {
+      const uint32_t j = again ? n - 1u : n;         // (again: the window held the first one too, n >= 1)
+      if (out && j >= skip && (uint64_t)(j - skip) < room) trace_record(L, step, out + (j - skip));
+      n = j + 1u;
+      // (the default variant never rewrites: the last kept record ends the lane)
+      if (!EARLY && out && n == total) return false;
+    }
+    return true;
+  }
+
+  // one iteration of the state machine; false once the lane has nothing left to do
+  __host__ __device__ __forceinline__ bool iter(Lane& L, const EvParams& p) {
+    const int32_t s0 = L.s;
+    EvOut o;
+    const bool done = L.step(p, o);
+    if (L.bailed) {                 // beyond the link capacities: no records, a zeroed result
+      status = PXB_TRACE_BAILED;
+      n = 0u;
+      return false;
+    }
+    if (done || L.s != s0) {
+      // an instance that ends at the step cap ends from its last visited step,
+      // s0, and its final step is step_cap - 1: both are recorded (the same state)
+      if (trace_cap_jump(done, o, L.s, s0) && !visit(L, (uint32_t)s0, false)) return false;
+      const uint32_t step = (uint32_t)(done ? L.s : s0);
+      if (!visit(L, step, EARLY && done && last_step == step)) return false;
+    }
+    if (done) {
+      res[0] = o.res[0];
+      res[1] = o.res[1];
+      res[2] = o.res[2];
+      res[3] = o.res[3];
+      return false;
+    }
+    return true;
+  }
+};
+
+// the config checks of pxb_trace_instance (host side), shared by pxb_trace_batch
+__host__ inline bool trace_config_ok(const pxb_config* cfg) {
+  if (cfg->n_proposers < 1 || cfg->n_proposers > PXB_MAX_PROPOSERS || cfg->n_acceptors < PXB_MIN_ACCEPTORS ||
+      cfg->n_acceptors > PXB_MAX_ACCEPTORS || cfg->delay_max < 1 || cfg->delay_max > PXB_MAX_DELAY ||
+      cfg->step_cap < 1 || !eligible(cfg))
+    return false;
+  // log mode (n_ticks > 1): eligible() holds its delays to the 8-step wheel
+  if (cfg->n_ticks > PXB_MAX_TICKS || (cfg->n_ticks > 1 && (cfg->tick_period < 1 || cfg->tick_period > PXB_MAX_STEP_CAP)))
+    return false;
+  return true;
+}
+
+}  // namespace ev
+}  // namespace pxb

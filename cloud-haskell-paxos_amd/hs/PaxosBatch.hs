@@ -37,6 +37,9 @@ module PaxosBatch
   , ProposerState (..)
   , TraceStep (..)
   , traceInstance
+  , TraceSel (..)
+  , allSteps
+  , traceBatch
     -- * Result queries (which instances to trace, without the results on the host)
   , Query (..)
   , FlagMode (..)
@@ -153,6 +156,10 @@ foreign import ccall safe "pxb_handoff_counts"
   c_pxb_handoff_counts :: CInt -> Ptr Word64 -> CInt -> IO CInt
 foreign import ccall safe "pxb_trace_instance"
   c_pxb_trace_instance :: Ptr BatchConfig -> Word64 -> Ptr Word32 -> Word32 -> Ptr Word32 -> Ptr Word32 -> IO CInt
+
+foreign import ccall safe "pxb_trace_batch"
+  c_pxb_trace_batch :: Ptr BatchConfig -> Ptr Word64 -> Word64 -> Ptr Word32 -> Ptr Word32 -> Word64 -> Ptr Word64
+                    -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
 
 foreign import ccall safe "pxb_sweep"
   c_pxb_sweep :: Ptr BatchConfig -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64
@@ -296,11 +303,13 @@ traceInstance cfg i maxRecords = do
             then Left <$> (c_pxb_strerror rc >>= peekCString)
             else do
               [n] <- peekArray 1 pn
-              recs <- forM [0 .. fromIntegral n - 1] $ \k -> step <$> peekArray nw (advancePtr pb (nw * k))
+              recs <- forM [0 .. fromIntegral n - 1] $ \k -> traceStep <$> peekArray nw (advancePtr pb (nw * k))
               [v, t, r, f] <- peekArray 4 pres
               pure (Right (recs, decode v t r f))
-  where
-    step w =
+
+-- | One pxb_trace_step (73 words) as a 'TraceStep'.
+traceStep :: [Word32] -> TraceStep
+traceStep w =
       let at k = w !! k
           nA = fromIntegral (at 2); nP = fromIntegral (at 3)
           cmd c = if c == 0 then Nothing else Just (commandOf c)
@@ -314,6 +323,61 @@ traceInstance cfg i maxRecords = do
                                    (cmd (at (b + 6))) (at (b + 7) /= 0)
       in TraceStep (fromIntegral (at 0)) (if at 1 == 0xFFFFFFFF then Nothing else Just (fromIntegral (at 1)))
                    (map acc [0 .. nA - 1]) (map pro [0 .. nP - 1])
+
+-- | pxb_trace_sel: which of an instance's records 'traceBatch' keeps: those
+-- with a step in the inclusive range, and of those only the last 'selTail'
+-- when it is not 0.
+data TraceSel = TraceSel
+  { selSteps :: !(Word32, Word32)
+  , selTail  :: !Word32
+  } deriving (Show)
+
+-- | Every record.
+allSteps :: TraceSel
+allSteps = TraceSel (0, maxBound) 0
+
+-- | pxb_trace_batch: the instances @ids@ of @cfg@ (any order, repeats allowed:
+-- typically the ids a 'sweep' lists) traced in one launch, 64 per wave.  For
+-- every id, in the order given: Nothing when the instance outgrew the per-lane
+-- state machine's link capacities (where 'traceInstance' fails), else the
+-- records the selection keeps and the instance's outcome.  Sizes the record
+-- buffer with a count-only call first.
+-- (additive to ABI 5: a library without the symbol fails to link)
+traceBatch :: BatchConfig -> [Word64] -> TraceSel -> IO (Either String [Maybe ([TraceStep], Outcome)])
+traceBatch cfg ids sel = do
+  let nw = 73                                      -- sizeof(pxb_trace_step) / 4
+      n = length ids
+      selw = [fst (selSteps sel), snd (selSteps sel), selTail sel, 0]
+      failed rc = Left <$> (c_pxb_strerror rc >>= peekCString)
+  with cfg $ \pc ->
+    withArray ids $ \pids ->
+      withArray selw $ \psel ->
+        allocaArray (n + 1) $ \poff ->
+          allocaArray (max 1 n) $ \pst ->
+            allocaArray (max 1 (4 * n)) $ \pres ->
+              allocaArray 1 $ \ptotal -> do
+                rc0 <- c_pxb_trace_batch pc pids (fromIntegral n) psel nullPtr 0 poff pst pres ptotal
+                if rc0 /= 0
+                  then failed rc0
+                  else do
+                    [total] <- peekArray 1 ptotal
+                    buf <- mallocForeignPtrArray (max 1 (nw * fromIntegral total))
+                    withForeignPtr buf $ \pb -> do
+                      rc <- if total == 0 then pure 0
+                            else c_pxb_trace_batch pc pids (fromIntegral n) psel pb total poff pst pres ptotal
+                      if rc /= 0
+                        then failed rc
+                        else do
+                          offs <- peekArray (n + 1) poff
+                          sts <- peekArray n pst
+                          Right <$> forM (zip3 [0 ..] (zip offs (drop 1 offs)) sts) (\(i, (o0, o1), st) ->
+                            if st /= 0
+                              then pure Nothing
+                              else do
+                                recs <- forM [fromIntegral o0 .. fromIntegral o1 - 1] $ \k ->
+                                  traceStep <$> peekArray nw (advancePtr pb (nw * k))
+                                [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                                pure (Just (recs, decode v t r f)))
 
 -- | pxb_query.flag_mode: how (flags .&. mask) is tested.
 data FlagMode = AnyOf | AllOf | NoneOf

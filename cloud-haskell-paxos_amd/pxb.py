@@ -92,7 +92,12 @@ class pxb_query(C.Structure):
                 ("n_bins_steps", C.c_uint32), ("n_bins_rounds", C.c_uint32)]
 
 
-assert C.sizeof(pxb_config) == 72 and C.sizeof(pxb_result) == 16
+class pxb_trace_sel(C.Structure):
+    _fields_ = [("step_min", C.c_uint32), ("step_max", C.c_uint32), ("tail", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(pxb_config) == 72 and C.sizeof(pxb_result) == 16 and C.sizeof(pxb_trace_sel) == 16
 assert C.sizeof(pxb_acceptor_rec) == 16 and C.sizeof(pxb_msg) == 16
 assert C.sizeof(pxb_query) == 32
 
@@ -239,7 +244,9 @@ def load(path: str = LIB_PATH):
                        ("pxb_init", [C.c_int]), ("pxb_shutdown", []),
                        ("pxb_trace_instance", [vp, C.c_uint64, vp, C.c_uint32, vp, vp]),
                        ("pxb_query_device", [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
-                       ("pxb_sweep", [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp])):
+                       ("pxb_sweep", [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_trace_batch_device", [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_trace_batch", [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
     lib.pxb_stream_release.argtypes = [C.c_int, vp]
@@ -492,13 +499,94 @@ def trace_instance(cfg: Config, instance: int, max_records: int = 8192, producti
     if production:
         c.flags |= CFG_TRACE_PRODUCTION
     check(lib.pxb_trace_instance(C.byref(c), instance, _ptr(buf), max_records, C.byref(nrec), _ptr(res)))
+    return trace_records(buf[:nrec.value]), res
+
+
+def trace_records(records):
+    """Decode pxb_trace_step rows (uint32 (k, TRACE_WORDS), as trace_batch returns
+    them) into the dicts trace_instance returns."""
     out = []
-    for r in buf[:nrec.value]:
+    for r in records:
         N, P = int(r[2]), int(r[3])
         out.append({"step": int(r[0]), "in_flight": int(r[1]),
                     "acc": r[4:4 + 36].reshape(9, 4)[:N].copy(), "digest": r[40:49][:N].copy(),
                     "prop": r[49:49 + 24].reshape(3, 8)[:P].copy()})
-    return out, res
+    return out
+
+
+TRACE_OK, TRACE_BAILED = 0, 1
+TRACE_BATCH_MAX = 1 << 30
+
+
+def _trace_cfg(cfg: Config, production: bool) -> pxb_config:
+    c = cfg.to_c(0, 1)
+    if production:
+        c.flags |= CFG_TRACE_PRODUCTION
+    return c
+
+
+def trace_batch(cfg: Config, ids, step_min: int = 0, step_max: int = U32_MAX, tail: int = 0, capacity=None,
+                production: bool = False):
+    """pxb_trace_batch: the instances `ids` (any order, repeats allowed) traced
+    in one launch.  Of every instance's per-step records (trace_instance's), those
+    with step_min <= step <= step_max are kept, cut to the last `tail` when tail
+    != 0.  Returns (records uint32 (k, TRACE_WORDS), offsets uint64 (n + 1,),
+    status uint32 (n,), results uint32 (n, 4)): instance i's records are
+    records[offsets[i]:offsets[i + 1]] (decode them with trace_records), status
+    TRACE_OK or TRACE_BAILED (beyond the state machine's link capacities, where
+    trace_instance raises: no records, a zeroed result).  capacity=None sizes the
+    record buffer with a count-only call first; with a capacity, k =
+    min(offsets[n], capacity) and the offsets stay the full ones."""
+    import numpy as np
+    lib = load()
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    n = len(ids)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint32)
+    res = np.zeros((n, 4), dtype=np.uint32)
+    c = _trace_cfg(cfg, production)
+    sel = pxb_trace_sel(step_min, step_max, tail, 0)
+    total = C.c_uint64(0)
+    args = (_ptr(offs), _ptr(status) if n else None, _ptr(res) if n else None, C.byref(total))
+    if capacity is None:
+        check(lib.pxb_trace_batch(C.byref(c), _ptr(ids) if n else None, n, C.byref(sel), None, 0, *args))
+        capacity = total.value
+        if capacity == 0:
+            return np.zeros((0, TRACE_WORDS), dtype=np.uint32), offs, status, res
+    rec =np.zeros((capacity, TRACE_WORDS), dtype=np.uint32)
+    check(lib.pxb_trace_batch(C.byref(c), _ptr(ids) if n else None, n, C.byref(sel), _ptr(rec) if capacity else None,
+                              capacity, *args))
+    return rec[:min(total.value, capacity)], offs, status, res
+
+
+def trace_batch_device(cfg: Config, d_ids, count: int, d_offsets, d_records=None, capacity: int = 0, d_status=None,
+                       d_results=None, step_min: int = 0, step_max: int = U32_MAX, tail: int = 0,
+                       production: bool = False, stream=None):
+    """pxb_trace_batch_device on torch tensors, asynchronous on `stream`: d_ids
+    int64 (count,), d_offsets int64 (count + 1,), d_records int32 (capacity,
+    TRACE_WORDS) or None with capacity 0 (the sizing call), d_status int32
+    (count,) and d_results int32 (count, 4) optional.  Records at or past
+    `capacity` are counted in the offsets and not written.  Sizes and dtypes
+    are checked here: the C ABI takes raw pointers."""
+    if d_offsets is None:
+        raise ValueError("d_offsets is required")
+    if count and d_ids is None:
+        raise ValueError("d_ids is required")
+    if capacity and d_records is None:
+        raise ValueError("d_records is required when capacity > 0")
+    if count > TRACE_BATCH_MAX:
+        raise ValueError("count: at most 2^30 instances a call")
+    _check_buf("d_ids", d_ids, count, 8)
+    _check_buf("d_offsets", d_offsets, count + 1, 8)
+    _check_buf("d_records", d_records, TRACE_WORDS * capacity, 4)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    lib = load()
+    c = _trace_cfg(cfg, production)
+    sel = pxb_trace_sel(step_min, step_max, tail, 0)
+    s = C.c_void_p(stream) if stream else None
+    check(lib.pxb_trace_batch_device(C.byref(c), _ptr(d_ids), count, C.byref(sel), _ptr(d_records) if capacity else None,
+                                     capacity, _ptr(d_offsets), _ptr(d_status), _ptr(d_results), s))
 
 
 def init(n_devices: int = 0):

@@ -220,7 +220,9 @@ void pxb_stream_release(int dev, void* stream);
  * per-lane state machine of the faulty kernels (csrc/paxos_ev.h) and records
  * the state at the end of every step it visits: steps with no due message and
  * no Tick change nothing and are skipped (their state is the previous
- * record's).  Host buffers; out holds max_records records; *n_records is the
+ * record's).  An instance that ends at the step cap because its next message
+ * falls due past it records its last visited step and then, with the same
+ * state, the final step step_cap - 1.  Host buffers; out holds max_records records; *n_records is the
  * count written (the last one is the final step); result (nullable) is the
  * instance's pxb_result, as pxb_run gives it.  By default the trace runs the
  * variant of the state machine in which every step sends all of its copies
@@ -434,6 +436,62 @@ int pxb_query_device(const pxb_result* d_results, uint64_t first_instance, uint6
 int pxb_sweep(const pxb_config* cfg, const pxb_query* q,
               uint64_t* ids, pxb_result* matched, uint64_t capacity, uint64_t* n_matches,
               int64_t* hist_steps, int64_t* hist_rounds, pxb_counters* totals);
+
+/* ---- batched trace (additive to ABI 5, found by symbol like the queries) ------
+ * The instances a sweep lists, traced in one launch: ids in, per-step records
+ * out, on the device.  Let R(id) be the records pxb_trace_instance(cfg, id, ...)
+ * returns with enough max_records (the same variant: default, or
+ * PXB_CFG_TRACE_PRODUCTION in cfg->flags; log mode when n_ticks > 1), and
+ * kept(id) those of R(id) whose step lies in [step_min, step_max], cut to the
+ * last `tail` of them when tail != 0.  Then
+ *   d_offsets[i]  = sum of |kept(d_ids[j])| over j < i   (count + 1 entries;
+ *                   d_offsets[count] is the total),
+ *   d_records[d_offsets[i] ...] = kept(d_ids[i]) in step order, byte for byte
+ *                   the pxb_trace_step records pxb_trace_instance writes,
+ *   d_status[i]   = PXB_TRACE_OK, or PXB_TRACE_BAILED for an instance that
+ *                   outgrew the per-lane state machine's link capacities (where
+ *                   pxb_trace_instance returns PXB_E_INVAL): kept is empty and
+ *                   d_results[i] is zeroed,
+ *   d_results[i]  = the instance's pxb_result, as pxb_run gives it.
+ * Output follows the order of d_ids: ids may be unsorted, repeated and on both
+ * sides of 2^32; cfg->first_instance and cfg->n_instances are ignored.  A record
+ * whose position is at or past `capacity` is counted in the offsets but not
+ * written, and nothing at or past `capacity` entries is touched.  d_records may
+ * be NULL only when capacity == 0: the sizing call (offsets, status and results
+ * only; the record-writing pass does not run).  d_status and d_results are
+ * nullable, d_offsets is required.  Asynchronous on `stream`, no device
+ * synchronisation.  PXB_E_INVAL, before any device call, for a null cfg or
+ * d_offsets, a null d_ids with count > 0, count > 2^30, sel->reserved != 0,
+ * d_records == NULL with capacity > 0, and every config pxb_trace_instance
+ * rejects.  count == 0 is valid and writes d_offsets[0] = 0.
+ * Two passes of one kernel (one 64-lane wave per block, lane l of block b runs
+ * d_ids[64 b + l]) with hipCUB's exclusive sum between them: the first counts,
+ * the second re-runs the (deterministic) instances and writes; no block waits
+ * for another.  Scratch (4 B per id + the scan's) comes from the per-device
+ * stream-ordered pool of the wire codec and the query, on the caller's stream. */
+#define PXB_TRACE_OK      0u
+#define PXB_TRACE_BAILED  1u   /* outgrew the per-lane state machine's link capacities
+                                  (where pxb_trace_instance returns PXB_E_INVAL): no records */
+typedef struct pxb_trace_sel {   /* 16 B; NULL = every record */
+  uint32_t step_min, step_max;   /* keep records with step_min <= step <= step_max (min > max: none) */
+  uint32_t tail;                 /* != 0: of those, only the last `tail` per instance */
+  uint32_t reserved;             /* must be 0 */
+} pxb_trace_sel;
+
+int pxb_trace_batch_device(const pxb_config* cfg, const uint64_t* d_ids, uint64_t count,
+                           const pxb_trace_sel* sel,
+                           pxb_trace_step* d_records, uint64_t capacity,
+                           uint64_t* d_offsets,      /* count + 1 entries, required */
+                           uint32_t* d_status,       /* count, nullable */
+                           pxb_result* d_results,    /* count, nullable */
+                           void* stream);
+/* pxb_trace_batch: HOST buffers, blocking, on the current device; PXB_E_NODEV
+ * without a GPU (checked after the validation above).  Runs the count pass,
+ * reads the total, and allocates min(total, capacity) records on the device,
+ * not `capacity`; *n_records (nullable) is the full total.                    */
+int pxb_trace_batch(const pxb_config* cfg, const uint64_t* ids, uint64_t count, const pxb_trace_sel* sel,
+                    pxb_trace_step* records, uint64_t capacity, uint64_t* offsets,
+                    uint32_t* status, pxb_result* results, uint64_t* n_records);
 
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
