@@ -7,7 +7,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <map>
 #include <mutex>
+#include <utility>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +20,7 @@
 #include "paxos_ff1.h"
 #include "paxos_ffp.h"
 #include "paxos_kernel.h"
+#include "route_plan.h"
 #include "sweep_plan.h"
 
 namespace pxb {
@@ -32,25 +35,15 @@ namespace pxb {
 PXB_FOR_MODES(PXB_EXTERN, 1)
 PXB_FOR_MODES(PXB_EXTERN, 2)
 PXB_FOR_MODES(PXB_EXTERN, 3)
-// per-lane kernels (paxos_ev.hip): P x N x {8, 16}-step wheels
-#define PXB_EV_EXTERN(PM, N, W, C) extern template __global__ void ev::paxos_ev_kernel<PM, N, W, C>(ev::EvKParams);
-#define PXB_EV_FOR(M, PM, W, C) M(PM, 2, W, C) M(PM, 3, W, C) M(PM, 4, W, C) M(PM, 5, W, C) M(PM, 6, W, C) \
-  M(PM, 7, W, C) M(PM, 8, W, C) M(PM, 9, W, C)
-PXB_EV_FOR(PXB_EV_EXTERN, 1, 8, false) PXB_EV_FOR(PXB_EV_EXTERN, 1, 16, false) PXB_EV_FOR(PXB_EV_EXTERN, 1, 8, true)
-PXB_EV_FOR(PXB_EV_EXTERN, 2, 8, false) PXB_EV_FOR(PXB_EV_EXTERN, 2, 16, false) PXB_EV_FOR(PXB_EV_EXTERN, 2, 8, true)
-PXB_EV_FOR(PXB_EV_EXTERN, 3, 8, false) PXB_EV_FOR(PXB_EV_EXTERN, 3, 16, false) PXB_EV_FOR(PXB_EV_EXTERN, 3, 8, true)
-#define PXB_EV_EXTERN_SL(PM, N, W, C) extern template __global__ void ev::paxos_ev_kernel<PM, N, W, C, false, true>(ev::EvKParams);
-PXB_EV_FOR(PXB_EV_EXTERN_SL, 1, 8, false) PXB_EV_FOR(PXB_EV_EXTERN_SL, 2, 8, false) PXB_EV_FOR(PXB_EV_EXTERN_SL, 3, 8, false)
-// (the compact 4-step, log-mode and simple-schedule shapes: instantiated in paxos_ev.hip too)
-PXB_EV_FOR(PXB_EV_EXTERN, 1, 4, true) PXB_EV_FOR(PXB_EV_EXTERN, 2, 4, true) PXB_EV_FOR(PXB_EV_EXTERN, 3, 4, true)
-#define PXB_EV_EXTERN_LG(PM, N, W, C) extern template __global__ void ev::paxos_ev_kernel<PM, N, W, C, true>(ev::EvKParams);
-PXB_EV_FOR(PXB_EV_EXTERN_LG, 1, 8, false) PXB_EV_FOR(PXB_EV_EXTERN_LG, 2, 8, false) PXB_EV_FOR(PXB_EV_EXTERN_LG, 3, 8, false)
-PXB_EV_FOR(PXB_EV_EXTERN_LG, 1, 16, false) PXB_EV_FOR(PXB_EV_EXTERN_LG, 2, 16, false) PXB_EV_FOR(PXB_EV_EXTERN_LG, 3, 16, false)
-#define PXB_EV_EXTERN_LGS(PM, N, W, C) extern template __global__ void ev::paxos_ev_kernel<PM, N, W, C, true, true>(ev::EvKParams);
-PXB_EV_FOR(PXB_EV_EXTERN_LGS, 1, 4, false) PXB_EV_FOR(PXB_EV_EXTERN_LGS, 2, 4, false) PXB_EV_FOR(PXB_EV_EXTERN_LGS, 3, 4, false)
-#define PXB_EV_EXTERN_SP(PM, N, W, SP) extern template __global__ void ev::paxos_ev_kernel<PM, N, W, true, false, false, SP>(ev::EvKParams);
-PXB_EV_FOR(PXB_EV_EXTERN_SP, 1, 4, 1) PXB_EV_FOR(PXB_EV_EXTERN_SP, 2, 4, 1) PXB_EV_FOR(PXB_EV_EXTERN_SP, 3, 4, 1)
-PXB_EV_FOR(PXB_EV_EXTERN_SP, 2, 4, 2)
+// per-lane kernels (paxos_ev.hip): every row of ev_layouts.h x its proposer counts x N
+#define PXB_EV_EXTERN(PM, N, W, C, L, S, SP) \
+  extern template __global__ void ev::paxos_ev_kernel<PM, N, W, C, L, S, SP>(ev::EvKParams);
+#define PXB_EV_EXTERN_N(PM, W, C, L, S, SP) PXB_EV_EXTERN(PM, 2, W, C, L, S, SP) PXB_EV_EXTERN(PM, 3, W, C, L, S, SP) \
+  PXB_EV_EXTERN(PM, 4, W, C, L, S, SP) PXB_EV_EXTERN(PM, 5, W, C, L, S, SP) PXB_EV_EXTERN(PM, 6, W, C, L, S, SP)     \
+  PXB_EV_EXTERN(PM, 7, W, C, L, S, SP) PXB_EV_EXTERN(PM, 8, W, C, L, S, SP) PXB_EV_EXTERN(PM, 9, W, C, L, S, SP)
+#define PXB_EV_ROW(ID, W, C, L, S, SP, PART, BUILT) PXB_EV_BUILT_##BUILT(PXB_EV_EXTERN_N, W, C, L, S, SP)
+PXB_EV_LAYOUTS(PXB_EV_ROW)
+#undef PXB_EV_ROW
 #define PXB_FF1_EXTERN(N) extern template __global__ void ff1::paxos_ff1_kernel<N>(ff1::Ff1Params);
 PXB_FF1_EXTERN(2) PXB_FF1_EXTERN(3) PXB_FF1_EXTERN(4) PXB_FF1_EXTERN(5)
 PXB_FF1_EXTERN(6) PXB_FF1_EXTERN(7) PXB_FF1_EXTERN(8) PXB_FF1_EXTERN(9)
@@ -96,11 +89,8 @@ __global__ void proposer_hook_kernel(pxb_proposer_rec* st, uint32_t n_acc, const
   nb[i] = no;
 }
 
-constexpr uint32_t QWORDS = 8;          // per-slot queue / counter words (finalize_kernel resets them)
-// queue words: [0] the general kernel's work queue, [1] the per-lane kernel's,
-// [2] its bailed-instance count; split routing: [3] the second per-lane
-// kernel's queue, [4] its bailed-instance count
-[[maybe_unused]] constexpr uint32_t Q_GEN = 0, Q_EV = 1, Q_BAIL = 2, Q_EV2 = 3, Q_BAIL2 = 4;   // (Q_GEN: kp.queue itself)
+// per-slot queue / counter words (finalize_kernel resets them; route_plan.h names the ones in use)
+constexpr uint32_t QWORDS = 8;
 
 // Sums the TCOPIES partial rows of the general kernel, and those of the
 // per-lane kernels unless the bailed-id list the general kernel ran
@@ -132,9 +122,9 @@ __global__ __launch_bounds__(TCOPIES) void finalize_kernel(unsigned long long* p
   if (t >= 16 && t < 16 + QWORDS) queue[t - 16] = 0u;
 }
 
-// the device's hand-off counts read (pxb_handoff_counts) of the device's hand-off counts (pxb_handoff_counts):
-// out[t] = the count, zeroed in the same atomic when reset, so a finalize_kernel
-// of another thread's chunk never adds between the read and the zeroing
+// The read of the device's hand-off counts (pxb_handoff_counts): out[t] = count
+// t, zeroed in the same atomic when reset, so a finalize_kernel of another
+// thread's chunk never adds between the read and the zeroing
 __global__ void hand_xchg_kernel(unsigned long long* h, unsigned long long* out, int reset) {
   const uint32_t t = threadIdx.x;
   if (t < 2) out[t] = reset ? atomicExch(&h[t], 0ull) : atomicAdd(&h[t], 0ull);
@@ -144,7 +134,7 @@ __global__ void hand_xchg_kernel(unsigned long long* h, unsigned long long* out,
 typedef void (*kernel_ptr)(KParams);
 typedef void (*ev_kernel_ptr)(ev::EvKParams);
 
-template <int PM, int W, bool C, bool L = false, bool S = false, int SP = 0>
+template <int PM, int W, bool C, bool L, bool S, int SP>
 static ev_kernel_ptr ev_pick_n(uint32_t n) {
   switch (n) {
     case 2: return ev::paxos_ev_kernel<PM, 2, W, C, L, S, SP>;
@@ -193,43 +183,15 @@ static ffp_kernel_ptr ffp_pick(uint32_t p, uint32_t n) {
   return p == 1 ? ffp_pick_n<1>(n) : p == 2 ? ffp_pick_n<2>(n) : p == 3 ? ffp_pick_n<3>(n) : nullptr;
 }
 
-// layout index: 0 = 8-step wheel, 1 = 16-step wheel, 2 / 3 = compact links (8- / 4-step wheel),
-// 4 = log mode (8-step wheel), 5 = slim (8-step wheel, byte reply seqs), 6 = layout 3 for
-// simple schedules (no loss, no Tick skew: ev::layout_for), 7 = layout 6 with halfword
-// response FIFOs (tight: the first launch of the two-proposer simple schedules, P = 2 only),
-// 8 = log mode on the 16-step wheel with its topology's larger pool (the second stage
-// behind layout 4 over <= 10 links), 9 = layout 4 slimmed (byte reply seqs in registers) on
-// the 4-step wheel (the first stage of log mode over <= 10 links with delays <= 4)
-static ev_kernel_ptr ev_pick(uint32_t pm, uint32_t n, int layout) {
-  switch (pm * 10 + (uint32_t)layout) {
-    case 10: return ev_pick_n<1, 8, false>(n);
-    case 11: return ev_pick_n<1, 16, false>(n);
-    case 12: return ev_pick_n<1, 8, true>(n);
-    case 13: return ev_pick_n<1, 4, true>(n);
-    case 14: return ev_pick_n<1, 8, false, true>(n);
-    case 15: return ev_pick_n<1, 8, false, false, true>(n);
-    case 16: return ev_pick_n<1, 4, true, false, false, 1>(n);
-    case 18: return ev_pick_n<1, 16, false, true>(n);
-    case 19: return ev_pick_n<1, 4, false, true, true>(n);
-    case 20: return ev_pick_n<2, 8, false>(n);
-    case 21: return ev_pick_n<2, 16, false>(n);
-    case 22: return ev_pick_n<2, 8, true>(n);
-    case 23: return ev_pick_n<2, 4, true>(n);
-    case 24: return ev_pick_n<2, 8, false, true>(n);
-    case 25: return ev_pick_n<2, 8, false, false, true>(n);
-    case 26: return ev_pick_n<2, 4, true, false, false, 1>(n);
-    case 27: return ev_pick_n<2, 4, true, false, false, 2>(n);
-    case 28: return ev_pick_n<2, 16, false, true>(n);
-    case 29: return ev_pick_n<2, 4, false, true, true>(n);
-    case 30: return ev_pick_n<3, 8, false>(n);
-    case 31: return ev_pick_n<3, 16, false>(n);
-    case 32: return ev_pick_n<3, 8, true>(n);
-    case 33: return ev_pick_n<3, 4, true>(n);
-    case 34: return ev_pick_n<3, 8, false, true>(n);
-    case 35: return ev_pick_n<3, 8, false, false, true>(n);
-    case 36: return ev_pick_n<3, 4, true, false, false, 1>(n);
-    case 38: return ev_pick_n<3, 16, false, true>(n);
-    case 39: return ev_pick_n<3, 4, false, true, true>(n);
+// the kernel of a per-lane stage (a row of ev_layouts.h at one of its proposer counts)
+static ev_kernel_ptr ev_pick(RouteStage s, uint32_t n) {
+  switch (s.pm * 10 + (uint32_t)s.layout) {
+#define PXB_EV_CASE(PM, ID, W, C, L, S, SP) \
+  case PM * 10 + ID: return ev_pick_n<PM, W, C, L, S, SP>(n);
+#define PXB_EV_ROW(ID, W, C, L, S, SP, PART, BUILT) PXB_EV_BUILT_##BUILT(PXB_EV_CASE, ID, W, C, L, S, SP)
+    PXB_EV_LAYOUTS(PXB_EV_ROW)
+#undef PXB_EV_ROW
+#undef PXB_EV_CASE
   }
   return nullptr;
 }
@@ -279,9 +241,12 @@ static kernel_fn pick(uint32_t pm, uint32_t n, bool logm, bool ff) {
 // which is not safe against a concurrent setenv (tests/conftest.py's
 // `hooks` helper sets them and reloads)
 struct Hooks {
-  bool no_ev, no_ff1, no_ffp, no_split, no_tight, no_lg2, no_lgs, fail_after_first, ff1_bail;
-  int bail_cap;                   // PXB_EV_BAIL_CAP (-1: the default)
-  int blocks_per_cu;              // PXB_BLOCKS_PER_CU (0: none)
+  RouteHooks route;               // PXB_NO_* and PXB_EV_BAIL_CAP (route_plan.h)
+  // tests only: PXB_FAIL_AFTER_FIRST=1 fails every chunk right after its first
+  // per-lane launch (the list and slot bookkeeping of the failure path);
+  // PXB_FF1_BAIL=1 hands every fault-free instance to the general kernel
+  bool fail_after_first, ff1_bail;
+  int blocks_per_cu;             // PXB_BLOCKS_PER_CU (0: none)
   int ff1_oversub, ffp_oversub;   // PXB_FF1_OVERSUB / PXB_FFP_OVERSUB (0: FF1_OVERSUB)
   char multi_fail_phase[16];      // PXB_MULTI_FAIL_PHASE / _DEVICE (paxos_multi.cpp)
   int multi_fail_device;
@@ -295,7 +260,8 @@ static thread_local int g_last_hip = 0;
 static unsigned long long* g_dbg = nullptr;
 #endif
 static std::mutex g_mu;
-static int g_occ[4][4][10][64];         // [logm*2+ff][pm][n][device] blocks per CU (0 = unknown)
+// blocks per CU that fit of (kernel, block size), per device (occ_blocks; absent or 0 = unknown)
+static std::map<std::pair<const void*, int>, int> g_occ[64];
 static int g_cus[64];
 // Per-launch scratch: QSLOTS slots per device, each two sets of TCOPIES
 // partial-total rows (16 x u64; the general kernel's and the per-lane
@@ -320,32 +286,13 @@ static bool g_slot_ev_set[64][QSLOTS];
 // (slot creation: a device's own lock, so that its allocation and wait never
 // hold up launches on other devices under g_mu)
 static std::mutex g_dev_mu[64];
-// Per-lane kernel: one launch per EV_CHUNK instances; its bailed ids go to a
-// list of EV_BAIL_CAP entries (16 MB) kept per (device, stream): launches of
-// one stream run in order, so they can share it.  Bails are rare
-// (BASELINE configs: <= 1.5 %); a chunk whose list overflows is re-run whole
-// by the general kernel (finalize_kernel then drops the per-lane totals).
-// Big chunks matter: each one ends with a tail (the slowest instances of the
-// last waves, then of the bailed ones on the general kernel); config 4 at 2^26
-// on one GPU: 2^24-instance chunks 1292.6 ms, 2^25 1283.8, 2^26 1277.3.  The
-// list holds 1/16 of a chunk (16 MB per slot).
-constexpr uint64_t EV_CHUNK = 1ull << 26;
-constexpr uint32_t EV_BAIL_CAP = 1u << 22;
-// split routing (fuzzed P = 3 batches, config 5): the per-lane kernel of a
-// two-proposer shape takes the instances that drew P <= 2 and lists the P = 3
-// ones (a third) with its bails for the three-proposer shape, so that list
-// holds half a chunk; split chunks are 2^25 instances (64 MB lists, allocated
-// for the slots split launches use; config 5 at 2^25: 34.9 M/s with 2^24
-// chunks, 36.2 with 2^25)
-constexpr uint64_t EV_SPLIT_CHUNK = 1ull << 25;
 // fault-free per-lane kernels: blocks per launch, in multiples of the resident
 // ones (the dispatcher then hands a freed CU the next block, which balances
 // waves that run slower; one 2^28 config-2 launch: x1 5.26 ms, x2 4.76, x4 4.42,
 // x8 4.30, x16 4.25)
 constexpr uint64_t FF1_OVERSUB = 16;
-constexpr uint32_t EV_SPLIT_CAP = (uint32_t)(EV_SPLIT_CHUNK / 2);
-// At most EV_LIST_STREAMS streams per device hold lists (created lazily, 16 MB
-// each + 64 MB for the two-stage routings).  An entry records an event behind
+// At most EV_LIST_STREAMS streams per device hold the bailed-id lists of
+// route_plan.h (created lazily, 16 MB each + 64 MB for the two-stage routings).  An entry records an event behind
 // the last launches that use its lists (on every exit of a chunk once one of
 // them is queued, failures included); they are enqueued with g_mu held, so
 // whoever takes the entry over later (a stream beyond EV_LIST_STREAMS evicting
@@ -365,9 +312,6 @@ struct EvLists {
 };
 static EvLists g_lists[64][EV_LIST_STREAMS];
 static int g_nlists[64], g_lnext[64];
-static int g_eocc[11][4][10][64];
-static int g_ff1occ[10][64];
-static int g_ffpocc[4][10][64];
 
 static int hip_fail(hipError_t e) {
   g_last_hip = (int)e;
@@ -427,7 +371,7 @@ int pxb_debug_wave_times(unsigned long long* out, unsigned max_waves) {
 int pxb_last_hip_error(void) { return g_last_hip; }
 
 // the bailed-id lists of (dev, stream) (callers hold g_mu until their launches
-// on the lists are enqueued and a ListUse has recorded the entry's event)
+// on the lists are enqueued and a RecordOnExit holds the entry's event)
 static int stream_lists(int dev, hipStream_t st, bool need_split, uint32_t** bail, uint32_t** split,
                         EvLists** ent) {
   EvLists* e = nullptr;
@@ -454,38 +398,20 @@ static int stream_lists(int dev, hipStream_t st, bool need_split, uint32_t** bai
   return PXB_OK;
 }
 
-// Records an entry's event behind the launches of a chunk that use its lists,
-// on every exit of the chunk (success or failure) once the first of them is
-// queued (g_mu held: declared after the chunk's lock, so destroyed before it)
-struct ListUse {
-  EvLists* e;
+// Records an event behind whatever a chunk queued on its stream, on every exit
+// of the chunk (success or failure): the chunk's scratch slot (g_slot_ev) and,
+// where it uses them, its lists (EvLists::ev).  `ev` null: nothing to record.
+// (g_mu held: declared after the chunk's lock, so destroyed before it)
+struct RecordOnExit {
+  hipEvent_t ev;
+  bool* set;                    // the event's "recorded" flag
   hipStream_t st;
-  bool queued = false;
-  ~ListUse() {
-    if (!e || !queued) return;
-    if (hipEventRecord(e->ev, st) == hipSuccess) {
-      e->ev_set = true;
-    } else {
-      // (no event behind these launches: wait for them here, so that a later
-      // owner taking the entry over cannot share the lists with them)
-      (void)hipStreamSynchronize(st);
-      e->ev_set = false;
-    }
-  }
-};
-
-// The same for the chunk's scratch slot (g_slot_ev), on every exit of the chunk
-struct SlotUse {
-  int dev, sidx;
-  hipStream_t st;
-  ~SlotUse() {
-    if (sidx < 0) return;
-    if (hipEventRecord(g_slot_ev[dev][sidx], st) == hipSuccess) {
-      g_slot_ev_set[dev][sidx] = true;
-    } else {
-      (void)hipStreamSynchronize(st);
-      g_slot_ev_set[dev][sidx] = false;
-    }
+  ~RecordOnExit() {
+    if (!ev) return;
+    *set = hipEventRecord(ev, st) == hipSuccess;
+    // (no event behind these launches: wait for them here, so that a later
+    // user of the slot, or a later owner of the lists, cannot share them)
+    if (!*set) (void)hipStreamSynchronize(st);
   }
 };
 
@@ -546,16 +472,16 @@ static void read_hooks_locked() {
     const char* v = getenv(name);
     return v ? atoi(v) : dflt;
   };
-  h.no_ev = flag("PXB_NO_EV");
-  h.no_ff1 = flag("PXB_NO_FF1");
-  h.no_ffp = flag("PXB_NO_FFP");
-  h.no_split = flag("PXB_NO_SPLIT");
-  h.no_tight = flag("PXB_NO_TIGHT");
-  h.no_lg2 = flag("PXB_NO_LG2");
-  h.no_lgs = flag("PXB_NO_LGS");
+  h.route.no_ev = flag("PXB_NO_EV");
+  h.route.no_ff1 = flag("PXB_NO_FF1");
+  h.route.no_ffp = flag("PXB_NO_FFP");
+  h.route.no_split = flag("PXB_NO_SPLIT");
+  h.route.no_tight = flag("PXB_NO_TIGHT");
+  h.route.no_lg2 = flag("PXB_NO_LG2");
+  h.route.no_lgs = flag("PXB_NO_LGS");
   h.fail_after_first = flag("PXB_FAIL_AFTER_FIRST");
   h.ff1_bail = flag("PXB_FF1_BAIL");
-  h.bail_cap = num("PXB_EV_BAIL_CAP", -1);
+  h.route.bail_cap = num("PXB_EV_BAIL_CAP", -1);
   h.blocks_per_cu = std::max(0, num("PXB_BLOCKS_PER_CU", 0));
   const int fo = num("PXB_FF1_OVERSUB", 0), po = num("PXB_FFP_OVERSUB", 0);
   h.ff1_oversub = (fo > 0 && fo <= 64) ? fo : 0;
@@ -690,162 +616,28 @@ int pxb_handoff_counts(int dev, uint64_t* out2, int reset) {
   return e == hipSuccess ? PXB_OK : hip_fail(e);
 }
 
-int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_digest,
-                   pxb_acceptor_rec* d_acc, int64_t* d_totals, void* stream) {
-  int rc = validate(cfg);
-  if (rc) return rc;
-  if (!d_totals) return PXB_E_INVAL;
-  if (cfg->n_instances == 0) return PXB_OK;
-  int dev = 0;
-  HIPCHK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return PXB_E_NODEV;
-  const Hooks hk = hooks();
-  const bool logm = cfg->n_ticks > 1;   // log mode: several Ticks per proposer
-  // fault-free schedule: no message is lost, delayed past the next step or sent
-  // to an isolated acceptor (Tick skew is allowed)
-  const bool ff = !(cfg->flags & PXB_CFG_RANDOMIZE) && cfg->loss_ppm == 0 && cfg->delay_max == 1 &&
-                  cfg->crash_ppm == 0;
-  // faulty single-decree batches run on the per-lane kernel (paxos_ev.h), its
-  // bailed instances on the general faulty kernel.  Per-lane beats the general
-  // kernel on every topology, even where its layout fits 3 waves per CU
-  // (MI355X, 2^22 instances, ms: config 5 148 vs 247; P = 3, N = 9 with delays
-  // to 12: 347 vs 689; P = 2, N = 9, delays to 12: 97 vs 247).
-  // PXB_NO_EV=1 forces the general kernel.
-  // (faulty log mode too: the per-lane kernel's log-mode fields, 8-step wheel)
-  bool use_ev = !ff && ev::eligible(cfg) && !hk.no_ev;
-  // tests: a smaller bailed-id list, to exercise its overflow path
-  const uint32_t bail_cap = hk.bail_cap >= 0 ? std::min<uint32_t>((uint32_t)hk.bail_cap, EV_BAIL_CAP) : EV_BAIL_CAP;
-  // fault-free single-proposer batches (configs 1, 2) run one instance per
-  // lane on paxos_ff1_kernel, its (never expected) bails on the general
-  // faulty kernel; PXB_NO_FF1=1 keeps them on the general fault-free kernel
-  const bool use_ff1 = ff && !logm && cfg->n_proposers == 1 && !hk.no_ff1;
-  // the other fault-free batches (duelling proposers, log mode) on
-  // paxos_ffp_kernel, its bails on the general faulty kernel; PXB_NO_FFP=1
-  // keeps them on the general fault-free kernel
-  const bool use_ffp = ff && !use_ff1 && !hk.no_ffp;
-  kernel_fn fn = pick(cfg->n_proposers, cfg->n_acceptors, logm, ff && !use_ff1 && !use_ffp);
-  if (!fn) return PXB_E_INVAL;
-  const ff1_kernel_ptr ffn = use_ff1 ? ff1_pick(cfg->n_acceptors) : nullptr;
-  if (use_ff1 && !ffn) return PXB_E_INVAL;
-  const ffp_kernel_ptr pfn = use_ffp ? ffp_pick(cfg->n_proposers, cfg->n_acceptors) : nullptr;
-  if (use_ffp && !pfn) return PXB_E_INVAL;
-  const int layout = ev::layout_for(cfg);
-  // Two-stage faulty log mode over <= 10 links: the log-mode shape (layout 4,
-  // a 19-word response pool: 86 words, 7 waves per CU) over the chunk, the
-  // same shape on the 16-step wheel with a 32-word pool (layout 8) over what
-  // it hands on (pool overflows: none in 4 million instances of
-  // extra.log_mode_faulty, host model; 2 per million with an 18-word pool),
-  // the general log-mode kernel over that one's.  A handed-on instance is one
-  // of the longest; on the general kernel it held a 2^20-instance call 4-5 ms
-  // and a 2^22 one up to 22 ms after the per-lane kernel, on layout 8 0.9-6 ms
-  // (kernel traces, profiles/r06_notes/lg_kernel_trace.txt,
-  // lg2_kernel_trace_2p20.txt).  PXB_NO_LG2=1 turns it off.
-  const bool may_lg2 = use_ev && layout == 4 && cfg->n_proposers * cfg->n_acceptors <= 10 && !hk.no_lg2;
-  // With delays <= 4 the first stage is layout 9: layout 4 with its reply seqs
-  // as bytes in registers, the 4-step wheel and its canonical log packed (14
-  // words), the same 19-word pool: 75 LDS words, 8 waves per CU instead of 7
-  // (residency sweep, faulty log mode at 2^22, PXB_BLOCKS_PER_CU 5 / 6 / 7:
-  // 32.7 / 29.6 / 27.5 ms; layout 9: 2^22 +5.6 %, 2^20 +2.5 %,
-  // profiles/r06_notes/ab_lg_layout9.txt).  PXB_NO_LGS=1 keeps layout 4.
-  const bool lgs = use_ev && layout == 4 && cfg->delay_max <= 4 && cfg->n_proposers * cfg->n_acceptors <= 10 &&
-                   !hk.no_lgs;
-  const int flayout = lgs ? 9 : layout;     // (the first per-lane stage's)
-  const int elayout = may_lg2 ? 8 : flayout;
-  const ev_kernel_ptr efn = use_ev ? ev_pick(cfg->n_proposers, cfg->n_acceptors, elayout) : nullptr;
-  if (use_ev && !efn) return PXB_E_INVAL;
-  // Split routing of fuzzed three-proposer batches (config 5): the
-  // two-proposer shape's layout fits more waves (config 5: 6 vs 4 per CU), so
-  // it runs first, over the chunk, and lists the instances that drew P = 3
-  // (bailed at init) for the three-proposer shape, whose own bails go to the
-  // general kernel.  PXB_NO_SPLIT=1 turns it off.
-  // tests only: PXB_FAIL_AFTER_FIRST=1 fails every chunk right after its first
-  // per-lane launch (the list and slot bookkeeping of the failure path)
-  const bool fail_after_first = hk.fail_after_first;
-  const bool may_split = use_ev && (cfg->flags & PXB_CFG_RANDOMIZE) && cfg->n_proposers == 3 && !hk.no_split;
-  // Tight routing of two-proposer simple schedules whose layout-6 lane takes
-  // more than 52 LDS words (config 4: 60 words, 10 waves per CU, so half the
-  // SIMDs run 2 waves and half 3): layout 7 (52 words, 12 waves per CU)
-  // runs over the chunk first and lists its bails (config 4: 0.5 %, nearly all
-  // a full 3-deep response FIFO) for layout 6 over that list, whose own bails
-  // go to the general kernel.  PXB_NO_TIGHT=1 turns it off.
-  // Only where its hand-off rate is measured small: N = 6, 7 (host model,
-  // tools/wave_model.cpp NACC=6/7/8 TIGHT=1 on config 4's schedule: 0.11 %,
-  // 0.76 %, 2.8 %; at N = 8 the tight lane has 53 words, so it would not reach
-  // 12 waves per CU anyway, and its 21-word pool serves 16 response links).
-  // A list that overflowed (above a quarter of the chunk) would have the
-  // general kernel re-run the whole chunk: exact, but slow.
-  const bool may_tight = use_ev && layout == 6 && cfg->n_proposers == 2 && cfg->n_acceptors >= 6 &&
-                         cfg->n_acceptors <= 7 && !hk.no_tight;
-  const ev_kernel_ptr sfn = may_split ? ev_pick(2, cfg->n_acceptors, layout)
-                            : may_tight ? ev_pick(2, cfg->n_acceptors, 7)
-                            : may_lg2 ? ev_pick(cfg->n_proposers, cfg->n_acceptors, flayout) : nullptr;
-  // (split: the two-stage routing of either kind)
-  bool split = false;
-  const hipStream_t st = (hipStream_t)stream;
-  int occ, cus, eocc = 0, socc = 0;
-  if (int rc2 = ensure_slots(dev)) return rc2;   // (not under g_mu: see ensure_slots)
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_cus[dev]) {
-      hipDeviceProp_t prop;
-      HIPCHK(hipGetDeviceProperties(&prop, dev));
-      g_cus[dev] = prop.multiProcessorCount;
-    }
-    int& o = g_occ[(logm ? 2 : 0) + ((ff && !use_ff1 && !use_ffp) ? 1 : 0)][cfg->n_proposers][cfg->n_acceptors][dev];
-    if (!o) {
-      int nb = 0;
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn.fn, 64 * fn.wpb, 0));
-      o = std::max(1, nb);
-    }
-    // Residency: the launch-bounds target (waves per SIMD x 4 SIMDs), even when
-    // a small kernel would fit more (measured: 4 -> 6 waves/SIMD costs 5 % on
-    // config 2: more, more often partially filled slot generations per wave).
-    const int target = 4 * fn.occ;
-    occ = std::min(o, std::max(1, target / fn.wpb));   // blocks per CU
-    cus = g_cus[dev];
-    auto ev_occ = [&](ev_kernel_ptr k, uint32_t pm, int lay, int* out) -> int {
-      int& eo = g_eocc[lay][pm][cfg->n_acceptors][dev];
-      if (!eo) {
-        int nb = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 64, 0));
-        eo = std::max(1, nb);
-      }
-      *out = eo;
-      return PXB_OK;
-    };
-    if (use_ff1) {
-      int& fo = g_ff1occ[cfg->n_acceptors][dev];
-      if (!fo) {
-        int nb = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)ffn, 256, 0));
-        fo = std::max(1, nb);
-      }
-      eocc = fo;
-    }
-    if (use_ffp) {
-      int& fo = g_ffpocc[cfg->n_proposers][cfg->n_acceptors][dev];
-      if (!fo) {
-        int nb = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)pfn, 256, 0));
-        fo = std::max(1, nb);
-      }
-      eocc = fo;
-    }
-    if (use_ev) {
-      if (int rc2 = ev_occ(efn, cfg->n_proposers, elayout, &eocc)) return rc2;
-      if (sfn) {
-        if (int rc2 = ev_occ(sfn, may_lg2 ? cfg->n_proposers : 2, may_tight ? 7 : flayout, &socc)) return rc2;
-        split = may_lg2 || socc > eocc;
-      }
-    }
-    if (hk.blocks_per_cu > 0) {                 // tests / experiments: cap residency
-      occ = std::min(occ, hk.blocks_per_cu);
-      if (eocc) eocc = std::min(eocc, hk.blocks_per_cu);
-      if (socc) socc = std::min(socc, hk.blocks_per_cu);
-    }
+// ---- pxb_run_device's pieces: occupancy, parameters, launches ----
+
+// Blocks per CU that fit of `fn` at `block` threads, queried once per device
+// and kernel (g_mu held).  Keyed by the kernel itself, so no routing can file
+// one kernel's figure under another's.
+static int occ_blocks(int dev, const void* fn, int block, int* out) {
+  int& o = g_occ[dev][std::make_pair(fn, block)];
+  if (!o) {
+    int nb = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, block, 0));
+    o = std::max(1, nb);
   }
+  *out = o;
+  return PXB_OK;
+}
+
+// the general kernel's launch parameters of a config (first_instance,
+// n_instances, the outputs and the slot: per chunk)
+static KParams make_kparams(const pxb_config* cfg) {
   KParams kp;
   memset(&kp, 0, sizeof(kp));
+  const bool logm = cfg->n_ticks > 1;
   kp.k0 = (uint32_t)cfg->seed;
   kp.k1 = (uint32_t)(cfg->seed >> 32);
   kp.n_prop = cfg->n_proposers;
@@ -862,137 +654,174 @@ int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_dig
   kp.cfg = ((cfg->flags & PXB_CFG_RANDOMIZE) ? CFG_RANDOMIZE : 0u) | (lt ? CFG_LOSSY : 0u) | (ct ? CFG_CRASHY : 0u);
   kp.loss_m1 = (uint32_t)(lt - 1ull);
   kp.crash_m1 = (uint32_t)(ct - 1ull);
+  return kp;
+}
+
+#ifdef PXB_WAVE_TIMES
+// diagnostic build only: the timeline buffer, for a launch of `waves` waves
+static int wave_times_buf(unsigned waves, unsigned long long** out) {
+  if (!g_wt) HIPCHK(hipMalloc(&g_wt, 6ull * 65536 * sizeof(unsigned long long)));
+  g_wt_waves = waves;
+  *out = g_wt;
+  return PXB_OK;
+}
+#endif
+
+// the general kernel, `grid` blocks; with `ids`: over the instances a per-lane
+// kernel listed there (their count in queue word `word`, the list's capacity `cap`)
+static hipError_t launch_general(const kernel_fn& fn, unsigned grid, hipStream_t st, KParams kp,
+                                 const uint32_t* ids = nullptr, uint32_t word = 0, uint32_t cap = 0) {
+  if (ids) {
+    kp.ids = ids;
+    kp.n_ids = kp.queue + word;
+    kp.ids_cap = cap;
+  }
+  hipLaunchKernelGGL(fn.fn, dim3(grid), dim3(64 * fn.wpb), 0, st, kp);
+  return hipGetLastError();
+}
+
+// A fault-free per-lane kernel (paxos_ff1.h / paxos_ffp.h) over the chunk of
+// `kp`, `grid` blocks, then the general kernel (`resident` blocks) over its
+// bailed ids.  `fp` arrives zeroed but for the fields only its kernel has.
+extern "C++" template <class Kernel, class Params>
+static hipError_t launch_fault_free(Kernel kernel, Params fp, unsigned grid, const kernel_fn& fn, unsigned resident,
+                                    hipStream_t st, const KParams& kp, uint32_t* bail, uint32_t cap, bool bail_all) {
+  fp.first_instance = kp.first_instance;
+  fp.k0 = kp.k0;
+  fp.k1 = kp.k1;
+  fp.skew_max = kp.skew_max;
+  fp.step_cap = kp.step_cap;
+  fp.n_instances = kp.n_instances;
+  fp.out = kp.out;
+  fp.dig = kp.dig;
+  fp.acc = kp.acc;
+  fp.part = kp.part + ROWS_U64;
+  fp.bail_ids = bail;
+  fp.bail_n = kp.queue + Q_BAIL;
+  fp.bail_cap = cap;
+  fp.bail_all = bail_all ? 1u : 0u;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, fp);
+  if (hipError_t e = hipGetLastError()) return e;
+  return launch_general(fn, resident, st, kp, bail, Q_BAIL, cap);
+}
+
+// Validate, plan (route_plan.h), query the occupancy of the plan's kernels,
+// resolve, then chunk by chunk launch what the plan says and finalize_kernel.
+int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_digest,
+                   pxb_acceptor_rec* d_acc, int64_t* d_totals, void* stream) {
+  int rc = validate(cfg);
+  if (rc) return rc;
+  if (!d_totals) return PXB_E_INVAL;
+  if (cfg->n_instances == 0) return PXB_OK;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return PXB_E_NODEV;
+  const Hooks hk = hooks();
+  RoutePlan plan = route_plan(cfg, hk.route);
+  const uint32_t N = cfg->n_acceptors;
+  const kernel_fn fn = pick(cfg->n_proposers, N, plan.logm, plan.ff);
+  const ff1_kernel_ptr ffn = plan.kind == ROUTE_FF1 ? ff1_pick(N) : nullptr;
+  const ffp_kernel_ptr pfn = plan.kind == ROUTE_FFP ? ffp_pick(cfg->n_proposers, N) : nullptr;
+  // (efn: the per-lane stage that hands on to the general kernel; sfn: the one over the chunk before it)
+  const ev_kernel_ptr efn = plan.kind == ROUTE_EV ? ev_pick(plan.second, N) : nullptr;
+  const ev_kernel_ptr sfn = plan.two_stage != TWO_NONE ? ev_pick(plan.first, N) : nullptr;
+  if (!fn || (plan.kind == ROUTE_FF1 && !ffn) || (plan.kind == ROUTE_FFP && !pfn) || (plan.kind == ROUTE_EV && !efn) ||
+      (plan.two_stage != TWO_NONE && !sfn))
+    return PXB_E_INVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  int occ, cus, eocc = 0, socc = 0;              // blocks per CU: general, last per-lane stage, first one
+  if (int rc2 = ensure_slots(dev)) return rc2;   // (not under g_mu: see ensure_slots)
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_cus[dev]) {
+      hipDeviceProp_t prop;
+      HIPCHK(hipGetDeviceProperties(&prop, dev));
+      g_cus[dev] = prop.multiProcessorCount;
+    }
+    cus = g_cus[dev];
+    if (int rc2 = occ_blocks(dev, (const void*)fn.fn, 64 * fn.wpb, &occ)) return rc2;
+    // Residency: the launch-bounds target (waves per SIMD x 4 SIMDs), even when
+    // a small kernel would fit more (measured: 4 -> 6 waves/SIMD costs 5 % on
+    // config 2: more, more often partially filled slot generations per wave).
+    occ = std::min(occ, std::max(1, 4 * fn.occ / fn.wpb));
+    if (ffn || pfn)
+      if (int rc2 = occ_blocks(dev, ffn ? (const void*)ffn : (const void*)pfn, 256, &eocc)) return rc2;
+    if (efn)
+      if (int rc2 = occ_blocks(dev, (const void*)efn, 64, &eocc)) return rc2;
+    if (sfn)
+      if (int rc2 = occ_blocks(dev, (const void*)sfn, 64, &socc)) return rc2;
+    plan = route_resolve(plan, socc, eocc);
+    if (hk.blocks_per_cu > 0) {                 // tests / experiments: cap residency
+      occ = std::min(occ, hk.blocks_per_cu);
+      if (eocc) eocc = std::min(eocc, hk.blocks_per_cu);
+      if (socc) socc = std::min(socc, hk.blocks_per_cu);
+    }
+  }
+  const bool two_stage = plan.two_stage != TWO_NONE;
+  KParams kp = make_kparams(cfg);
   unsigned long long* const totals = reinterpret_cast<unsigned long long*>(d_totals);
 #ifdef PXB_STAMPS
-  {
-    static unsigned long long* dbg = nullptr;
-    if (!dbg) {
-      HIPCHK(hipMalloc(&dbg, 16 * sizeof(unsigned long long)));
-      HIPCHK(hipMemset(dbg, 0, 16 * sizeof(unsigned long long)));
-    }
-    kp.dbg = dbg;
-    g_dbg = dbg;
+  if (!g_dbg) {
+    HIPCHK(hipMalloc(&g_dbg, 16 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(g_dbg, 0, 16 * sizeof(unsigned long long)));
   }
+  kp.dbg = g_dbg;
 #endif
-  const uint64_t G = 64 / cfg->n_acceptors;
+  const uint64_t G = 64 / N, wpb = (uint64_t)fn.wpb;
   const uint64_t resident = (uint64_t)occ * (uint64_t)cus;
-  // a launch must not give any slot 65536 instances (16-bit packed run totals):
-  // on average 30000 per slot for the block-queue kernels (uniform instance
-  // lengths), 60000 for the work-queue kernels (which also flush mid-run);
-  // epoch tags (idx + 1 under the work queue) stay below 2^30.  Per-lane
-  // chunks are bounded by the bailed-id buffer of a scratch slot.
-  const uint64_t wpb = (uint64_t)fn.wpb;
-  // fault-free log mode: 16-bit epochs, so every block's range (static slices:
-  // every wave's) stays below 2^16 instances
-  // (tight: bails are rare, so whole chunks; the list holds a quarter of one)
-  // (log mode's second stage too)
-  const uint64_t ev_chunk = (split && !may_tight && !may_lg2) ? EV_SPLIT_CHUNK : EV_CHUNK;
-  // fault-free per-lane kernels: as few launches as the general faulty kernel
-  // allows (it may have to re-run a whole chunk); A/B on config 2 at 2^26:
-  // 2^24-instance launches 2 % slower, 2^22 10 %, 2^20 33 %
-  const uint64_t chunk_max = (use_ff1 || use_ffp) ? std::min<uint64_t>((1ull << 30) - 1, resident * wpb * G * 60000ull)
-                             : use_ev ? ev_chunk
-                             : (ff && logm) ? std::min<uint64_t>(resident * wpb * G * 30000ull, resident * 60000ull)
-                             : ff ? std::min<uint64_t>(1ull << 31, resident * wpb * G * 30000ull)
-                                  : std::min<uint64_t>((1ull << 30) - 1, resident * wpb * G * 60000ull);
+  const uint64_t chunk_max = route_chunk_max(plan, resident, wpb, G);
   for (uint64_t done = 0; done < cfg->n_instances; done += chunk_max) {
     const uint64_t nc = std::min<uint64_t>(chunk_max, cfg->n_instances - done);
     kp.first_instance = cfg->first_instance + done;
     kp.n_instances = (uint32_t)nc;
     kp.out = d_out ? reinterpret_cast<uint4*>(d_out + done) : nullptr;
-    kp.dig = d_log_digest ? d_log_digest + done * cfg->n_acceptors : nullptr;
-    kp.acc = d_acc ? reinterpret_cast<uint4*>(d_acc + done * cfg->n_acceptors) : nullptr;
+    kp.dig = d_log_digest ? d_log_digest + done * N : nullptr;
+    kp.acc = d_acc ? reinterpret_cast<uint4*>(d_acc + done * N) : nullptr;
     uint32_t *bail = nullptr, *slist = nullptr;
-    unsigned long long* slot = nullptr;
     EvLists* lent = nullptr;
     // (held until this chunk's launches are enqueued: see EvLists)
     std::unique_lock<std::mutex> lk(g_mu);
     const int sidx = (int)(g_qseq[dev]++ % QSLOTS);
-    slot = g_slots[dev] + (size_t)sidx * SLOT_U64;
+    unsigned long long* const slot = g_slots[dev] + (size_t)sidx * SLOT_U64;
     kp.part = slot;
     kp.queue = reinterpret_cast<uint32_t*>(slot + 2 * ROWS_U64);
     // after the slot's last user (another stream's chunk may still run on it)
     if (g_slot_ev_set[dev][sidx]) HIPCHK(hipStreamWaitEvent(st, g_slot_ev[dev][sidx], 0));
     // the slot's event goes behind whatever this chunk queues, on every exit
-    SlotUse suse{dev, sidx, st};
-    if (use_ev || use_ff1 || use_ffp)
-      if (int rc2 = stream_lists(dev, st, split, &bail, &slist, &lent)) return rc2;
+    RecordOnExit slot_use{g_slot_ev[dev][sidx], &g_slot_ev_set[dev][sidx], st};
+    if (plan.kind != ROUTE_GENERAL)
+      if (int rc2 = stream_lists(dev, st, two_stage, &bail, &slist, &lent)) return rc2;
     // the lists' event likewise
-    ListUse use{lent, st, lent != nullptr};
+    RecordOnExit list_use{lent ? lent->ev : nullptr, lent ? &lent->ev_set : nullptr, st};
     // a launch that fails after an earlier one of this chunk has queued leaves
     // the slot half used: zero it behind the queued work before reporting
     auto fail = [&](hipError_t e) {
       (void)hipMemsetAsync(slot, 0, SLOT_U64 * sizeof(unsigned long long), st);
       return hip_fail(e);
     };
-    uint32_t bail_word = Q_BAIL;
-    if (use_ff1) {
-      // the fault-free per-lane kernel over the chunk, the general kernel over its bailed ids
-      ff1::Ff1Params fp;
-      memset(&fp, 0, sizeof(fp));
-      fp.first_instance = kp.first_instance;
-      fp.k0 = kp.k0;
-      fp.k1 = kp.k1;
-      fp.skew_max = cfg->skew_max;
-      fp.step_cap = cfg->step_cap;
-      fp.n_instances = (uint32_t)nc;
-      fp.out = kp.out;
-      fp.dig = kp.dig;
-      fp.acc = kp.acc;
-      fp.part = kp.part + ROWS_U64;
-      fp.bail_ids = bail;
-      fp.bail_n = kp.queue + Q_BAIL;
-      fp.bail_cap = bail_cap;
-      fp.bail_all = hk.ff1_bail ? 1u : 0u;               // tests: hand every instance to the general kernel
-      // FF1_OVERSUB x the resident blocks (PXB_FF1_OVERSUB=k: k, A/B)
-      const uint64_t over = hk.ff1_oversub ? (uint64_t)hk.ff1_oversub : FF1_OVERSUB;
-      const uint64_t fres = (uint64_t)eocc * (uint64_t)cus * over;
+    if (plan.kind == ROUTE_FF1 || plan.kind == ROUTE_FFP) {
+      // FF1_OVERSUB x the resident blocks (PXB_FF1_OVERSUB / PXB_FFP_OVERSUB=k: k, A/B)
+      const int over = plan.kind == ROUTE_FF1 ? hk.ff1_oversub : hk.ffp_oversub;
+      const uint64_t fres = (uint64_t)eocc * (uint64_t)cus * (over ? (uint64_t)over : FF1_OVERSUB);
       const unsigned fgrid = (unsigned)std::min<uint64_t>((nc + 255) / 256, fres);
-      hipLaunchKernelGGL(ffn, dim3(fgrid), dim3(256), 0, st, fp);
-      if (hipError_t e = hipGetLastError()) return fail(e);
-      kp.ids = bail;
-      kp.n_ids = kp.queue + Q_BAIL;
-      kp.ids_cap = bail_cap;
-      hipLaunchKernelGGL(fn.fn, dim3((unsigned)resident), dim3(64 * fn.wpb), 0, st, kp);
-      if (hipError_t e = hipGetLastError()) return fail(e);
-    } else if (use_ffp) {
-      // the fault-free per-lane kernel for duelling proposers / log mode, then
-      // the general faulty kernel over its bailed ids
-      ffp::FfpParams fp;
-      memset(&fp, 0, sizeof(fp));
-      fp.first_instance = kp.first_instance;
-      fp.k0 = kp.k0;
-      fp.k1 = kp.k1;
-      fp.n_prop = cfg->n_proposers;
-      fp.skew_max = cfg->skew_max;
-      fp.step_cap = cfg->step_cap;
-      fp.n_ticks = kp.n_ticks;
-      fp.tick_period = kp.tick_period;
-      fp.n_instances = (uint32_t)nc;
-      fp.out = kp.out;
-      fp.dig = kp.dig;
-      fp.acc = kp.acc;
-      fp.part = kp.part + ROWS_U64;
-      fp.bail_ids = bail;
-      fp.bail_n = kp.queue + Q_BAIL;
-      fp.bail_cap = bail_cap;
-      fp.bail_all = hk.ff1_bail ? 1u : 0u;               // tests: hand every instance to the general kernel
-      const uint64_t over = hk.ffp_oversub ? (uint64_t)hk.ffp_oversub : FF1_OVERSUB;   // (A/B)
-      const uint64_t fres = (uint64_t)eocc * (uint64_t)cus * over;
-      const unsigned fgrid = (unsigned)std::min<uint64_t>((nc + 255) / 256, fres);
-      hipLaunchKernelGGL(pfn, dim3(fgrid), dim3(256), 0, st, fp);
-      if (hipError_t e = hipGetLastError()) return fail(e);
-      kp.ids = bail;
-      kp.n_ids = kp.queue + Q_BAIL;
-      kp.ids_cap = bail_cap;
-      hipLaunchKernelGGL(fn.fn, dim3((unsigned)resident), dim3(64 * fn.wpb), 0, st, kp);
-      if (hipError_t e = hipGetLastError()) return fail(e);
-    } else if (use_ev) {
-      // the per-lane kernel over the chunk, then the general kernel over its
-      // bailed ids; split: the two-proposer shape over the chunk, the
-      // three-proposer shape over its list, the general kernel over that one's;
-      // tight: layout 7 over the chunk, layout 6 over its list, the general
-      // kernel over that one's
+      hipError_t e;
+      if (plan.kind == ROUTE_FF1) {
+        ff1::Ff1Params fp;
+        memset(&fp, 0, sizeof(fp));
+        e = launch_fault_free(ffn, fp, fgrid, fn, (unsigned)resident, st, kp, bail, plan.cap, hk.ff1_bail);
+      } else {
+        ffp::FfpParams fp;
+        memset(&fp, 0, sizeof(fp));
+        fp.n_prop = cfg->n_proposers;
+        fp.n_ticks = kp.n_ticks;
+        fp.tick_period = kp.tick_period;
+        e = launch_fault_free(pfn, fp, fgrid, fn, (unsigned)resident, st, kp, bail, plan.cap, hk.ff1_bail);
+      }
+      if (e) return fail(e);
+    } else if (plan.kind == ROUTE_EV) {
+      // the last per-lane stage over the chunk, or (two-stage) the first one
+      // over the chunk and the last over its list; then the general kernel
+      // over the last stage's bailed ids
       ev::EvKParams ek;
       memset(&ek, 0, sizeof(ek));
       ek.p = ev::make_params(cfg);
@@ -1005,58 +834,45 @@ int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_dig
       ek.queue = kp.queue + Q_EV;
       ek.bail_ids = bail;
       ek.bail_n = kp.queue + Q_BAIL;
-      ek.bail_cap = bail_cap;
-      if (split) {
+      ek.bail_cap = plan.cap;
+      if (two_stage) {
         ev::EvKParams sk = ek;
         sk.bail_ids = slist;
-        sk.bail_cap = std::min<uint32_t>(bail_cap == EV_BAIL_CAP ? EV_SPLIT_CAP : bail_cap, EV_SPLIT_CAP);
+        sk.bail_cap = plan.first_cap;
         const unsigned sgrid = (unsigned)std::min<uint64_t>((nc + 63) / 64, (uint64_t)socc * (uint64_t)cus);
 #ifdef PXB_WAVE_TIMES   // (two-stage: the first per-lane launch's timeline)
-        if (!g_wt) HIPCHK(hipMalloc(&g_wt, 6ull * 65536 * sizeof(unsigned long long)));
-        sk.dbg = g_wt;
-        g_wt_waves = sgrid;
+        if (int rc2 = wave_times_buf(sgrid, &sk.dbg)) return rc2;
 #endif
         hipLaunchKernelGGL(sfn, dim3(sgrid), dim3(64), 0, st, sk);
         if (hipError_t e = hipGetLastError()) return fail(e);
         // (tests: a launch failure right after the first per-lane launch)
-        if (fail_after_first) return fail(hipErrorLaunchFailure);
+        if (hk.fail_after_first) return fail(hipErrorLaunchFailure);
         ek.ids = slist;
         ek.n_ids = kp.queue + Q_BAIL;
-        ek.ids_cap = sk.bail_cap;
+        ek.ids_cap = plan.first_cap;
         ek.queue = kp.queue + Q_EV2;
         ek.bail_n = kp.queue + Q_BAIL2;
-        bail_word = Q_BAIL2;
       }
-      const uint64_t eres = (uint64_t)eocc * (uint64_t)cus;
-      const unsigned egrid = (unsigned)std::min<uint64_t>((nc + 63) / 64, eres);
+      const unsigned egrid = (unsigned)std::min<uint64_t>((nc + 63) / 64, (uint64_t)eocc * (uint64_t)cus);
 #ifdef PXB_WAVE_TIMES
-      if (!g_wt) HIPCHK(hipMalloc(&g_wt, 6ull * 65536 * sizeof(unsigned long long)));
-      ek.dbg = split ? nullptr : g_wt;
-      if (!split) g_wt_waves = egrid;
+      if (!two_stage)
+        if (int rc2 = wave_times_buf(egrid, &ek.dbg)) return rc2;
 #endif
       hipLaunchKernelGGL(efn, dim3(egrid), dim3(64), 0, st, ek);
       if (hipError_t e = hipGetLastError()) return fail(e);
-      if (fail_after_first) return fail(hipErrorLaunchFailure);
-      kp.ids = bail;
-      kp.n_ids = kp.queue + bail_word;
-      kp.ids_cap = bail_cap;
-      hipLaunchKernelGGL(fn.fn, dim3((unsigned)resident), dim3(64 * fn.wpb), 0, st, kp);
-      if (hipError_t e = hipGetLastError()) return fail(e);
+      if (hk.fail_after_first) return fail(hipErrorLaunchFailure);
+      if (hipError_t e = launch_general(fn, (unsigned)resident, st, kp, bail, plan.bail_word, plan.cap)) return fail(e);
     } else {
-      const uint64_t waves_needed = (nc + G - 1) / G;
-      const uint64_t blocks_needed = (waves_needed + wpb - 1) / wpb;
+      const uint64_t blocks_needed = ((nc + G - 1) / G + wpb - 1) / wpb;
       const unsigned grid = (unsigned)std::min<uint64_t>(blocks_needed, resident);
 #ifdef PXB_WAVE_TIMES
-      if (!g_wt) HIPCHK(hipMalloc(&g_wt, 6ull * 65536 * sizeof(unsigned long long)));
-      kp.dbg = g_wt;
-      g_wt_waves = grid * fn.wpb;
       if (grid * fn.wpb > 65536) return PXB_E_INVAL;
+      if (int rc2 = wave_times_buf(grid * fn.wpb, &kp.dbg)) return rc2;
 #endif
-      hipLaunchKernelGGL(fn.fn, dim3(grid), dim3(64 * fn.wpb), 0, st, kp);
-      HIPCHK(hipGetLastError());
+      HIPCHK(launch_general(fn, grid, st, kp));
     }
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(TCOPIES), 0, st, kp.part, kp.part + ROWS_U64, kp.queue,
-                       bail_word, bail_cap, totals, g_slots[dev] + HAND_U64);
+                       plan.bail_word, plan.cap, totals, g_slots[dev] + HAND_U64);
     if (hipError_t e = hipGetLastError()) return fail(e);
   }
   return PXB_OK;

@@ -54,6 +54,7 @@
 #include <type_traits>
 
 #include "../../include/paxos_batch.h"
+#include "ev_layouts.h"
 #include "paxos_device.h"
 
 namespace pxb {
@@ -72,8 +73,6 @@ namespace ev {
 #define PXB_EV_PQ_CAP 4
 #endif
 constexpr uint32_t PQ_CAP = PXB_EV_PQ_CAP;    // pending broadcasts per lane
-constexpr uint32_t MAX_STEP_CAP = 4095;   // 12-bit tickets (tickets <= step_cap, SEMANTICS §6)
-static_assert(MAX_STEP_CAP < PXB_TICKET_LIMIT, "EV tickets never reach the overflow limit");
 
 // lane modes
 constexpr uint32_t M_IDLE = 0, M_RUN = 1;
@@ -1340,20 +1339,6 @@ struct EvLane {
   }
 };
 
-// EV eligibility of a launch (host side): single decree, faulty, 12-bit tickets,
-// delays inside the 16-step wheel.  Fault-free and log-mode batches keep the
-// paxos_kernel.h kernels.
-__host__ inline bool eligible(const pxb_config* c) {
-  // (log mode: the 8-step wheel layout only)
-  return c->step_cap <= MAX_STEP_CAP && c->delay_max <= (c->n_ticks > 1 ? 8u : 15u);
-}
-
-}  // namespace ev
-}  // namespace pxb
-
-namespace pxb {
-namespace ev {
-
 // Launch parameters from the ABI config (host side; mirrors pxb_run_device).
 __host__ inline EvParams make_params(const pxb_config* c) {
   EvParams p{};
@@ -1377,49 +1362,6 @@ __host__ inline EvParams make_params(const pxb_config* c) {
   p.crash_m1 = (uint32_t)(ct - 1ull);
   return p;
 }
-
-// the timing wheel must outlast the longest delay: sends at step s (or s - 1
-// for a carried-over copy) fall due in [s, s + delay_max] (a link's FIFO tail
-// is at most its last send step + delay_max), the slot of s is emptied on
-// entering s and a copy due at s goes straight to the step's due links, so
-// the wheel holds dues in [s + 1, s + delay_max]: 8 slots serve delays up to 8
-// (4 slots up to 4)
-__host__ inline int wheel_for(uint32_t delay_max) { return delay_max <= 8 ? 8 : 16; }
-
-// Kernel layout of a launch: 0 = 8-step wheel, 1 = 16-step wheel, 2 = compact
-// links (3-entry request FIFOs sharing a word with the reply seq, a 24-word
-// response pool, 8-step wheel).  Short delays keep FIFOs short (BASELINE
-// config 4: 0.9 % of instances ever hold a fourth request on one link, config
-// 3: 0.02 %; those are bailed to the general kernel), so they take the compact
-// layout, which fits more resident waves; fuzzed or long-delay schedules keep
-// 4-entry FIFOs.  The compact reply seq has 9 bits (config 4 reaches 68 in 256
-// steps), so long runs keep the separate 16-bit one; three duelling proposers
-// over 9 acceptors overflow the 3-entry FIFOs too often (25 % of instances at
-// 10 % loss), so the compact layout is kept to topologies of <= 16 links.
-// Layout 3 is the compact layout with a 4-step wheel (delays up to 4: BASELINE
-// configs 3 and 4), 4 words per lane fewer.  Layout 5 is layout 0 slimmed
-// (Shape::SL) for runs of at most 512 steps (BASELINE config 5).
-__host__ inline int layout_for(const pxb_config* c) {
-  if (c->n_ticks > 1) return 4;                      // log mode: 8-step wheel, 4-entry FIFOs, LG fields
-  if (!(c->flags & PXB_CFG_RANDOMIZE) && c->delay_max <= 4 && c->step_cap <= 512 &&
-      c->n_proposers * c->n_acceptors <= 16)
-    return (c->loss_ppm == 0 && c->skew_max == 0) ? 6 : 3;   // 6: layout 3, simple schedule (Shape::SP)
-  if (wheel_for(c->delay_max) != 8) return 1;
-#ifndef PXB_EV_NO_SLIM
-  if (c->step_cap <= 512) return 5;                  // slim: byte reply seqs suffice
-#endif
-  return 0;
-}
-__host__ inline int layout_wheel(int layout) {
-  return (layout == 1 || layout == 8) ? 16 : (layout == 3 || layout == 6 || layout == 7 || layout == 9) ? 4 : 8;
-}
-__host__ inline bool layout_compact(int layout) { return layout == 2 || layout == 3 || layout == 6 || layout == 7; }
-__host__ inline bool layout_simple(int layout) { return layout == 6 || layout == 7; }
-// (8: layout 4 on the 16-step wheel with its topology's larger pool, the
-// second stage of two-stage log mode, pxb_run_device)
-// (9: layout 4 slimmed -- byte reply seqs in registers -- on the 4-step wheel,
-// for log mode with delays <= 4 over <= 10 links: the first stage there)
-__host__ inline bool layout_log(int layout) { return layout == 4 || layout == 8 || layout == 9; }
 
 }  // namespace ev
 }  // namespace pxb

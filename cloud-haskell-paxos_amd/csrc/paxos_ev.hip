@@ -1,9 +1,9 @@
 // paxos_ev.hip — explicit instantiations of the per-lane kernel
-// (paxos_ev_kernel.h) for one proposer count (-DPXB_EV_P=1|2|3): 8 acceptor
-// counts x {8, 16}-step timing wheels (plus the compact-link
-// layout with the 8- and 4-step wheels, the log-mode fields on the 8-step
-// wheel, the slim 8-step layout, and the tight layout 7 for P = 2).  Split by P so the units build in
-// parallel.
+// (paxos_ev_kernel.h) for one proposer count (-DPXB_EV_P=1|2|3): every layout
+// of ev_layouts.h built for that count, over the 8 acceptor counts.  Split by P
+// and by part (-DPXB_EV_PART=0|1; neither: both) -- two units per proposer
+// count, so that each builds in parallel and takes its own scheduler flags,
+// __graft_entry__.py.
 #include "paxos_ev_kernel.h"
 
 #if !defined(PXB_EV_P)
@@ -16,24 +16,24 @@ namespace ev {
 #define PXB_EV_FOR_N(W, C, L, S, SP) PXB_EV_INST(2, W, C, L, S, SP) PXB_EV_INST(3, W, C, L, S, SP) \
   PXB_EV_INST(4, W, C, L, S, SP) PXB_EV_INST(5, W, C, L, S, SP) PXB_EV_INST(6, W, C, L, S, SP) \
   PXB_EV_INST(7, W, C, L, S, SP) PXB_EV_INST(8, W, C, L, S, SP) PXB_EV_INST(9, W, C, L, S, SP)
-// (PXB_EV_PART 0: the wide, compact and simple-schedule shapes; 1: the log-mode
-// and slim ones -- two units per proposer count, so that each builds in
-// parallel and takes its own scheduler flags, __graft_entry__.py)
-#if !defined(PXB_EV_PART) || PXB_EV_PART == 0
-PXB_EV_FOR_N(8, false, false, false, false)
-PXB_EV_FOR_N(16, false, false, false, false)
-PXB_EV_FOR_N(8, true, false, false, false)
-PXB_EV_FOR_N(4, true, false, false, false)
-PXB_EV_FOR_N(4, true, false, false, 1)         // simple schedule (layout 6)
+// a row's instantiations, when this unit is its part and its proposer count is built
+#define PXB_EV_IF_ALL(...) __VA_ARGS__
 #if PXB_EV_P == 2
-PXB_EV_FOR_N(4, true, false, false, 2)         // tight simple schedule (layout 7; two proposers only)
+#define PXB_EV_IF_P2(...) __VA_ARGS__
+#else
+#define PXB_EV_IF_P2(...)
 #endif
+#if !defined(PXB_EV_PART) || PXB_EV_PART == 0
+#define PXB_EV_IF_PART0(...) __VA_ARGS__
+#else
+#define PXB_EV_IF_PART0(...)
 #endif
 #if !defined(PXB_EV_PART) || PXB_EV_PART == 1
-PXB_EV_FOR_N(8, false, true, false, false)     // log mode
-PXB_EV_FOR_N(16, false, true, false, false)    // log mode, second stage (layout 8: 16-step wheel, larger pool)
-PXB_EV_FOR_N(8, false, false, true, false)     // slim
-PXB_EV_FOR_N(4, false, true, true, false)      // log mode, slim, 4-step wheel (layout 9)
+#define PXB_EV_IF_PART1(...) __VA_ARGS__
+#else
+#define PXB_EV_IF_PART1(...)
 #endif
+#define PXB_EV_ROW(ID, W, C, L, S, SP, PART, BUILT) PXB_EV_IF_PART##PART(PXB_EV_IF_##BUILT(PXB_EV_FOR_N(W, C, L, S, SP)))
+PXB_EV_LAYOUTS(PXB_EV_ROW)
 }  // namespace ev
 }  // namespace pxb

@@ -154,7 +154,7 @@ int run_n(const pxb_config* c, pxb_result* o, uint32_t* d, pxb_acceptor_rec* a, 
   return -1;
 }
 
-template <int W, bool CMP, bool LG = false, bool SL = false, int SP = 0>
+template <int W, bool CMP, bool LG, bool SL, int SP>
 int run_w(const pxb_config* c, uint32_t pm, pxb_result* o, uint32_t* d, pxb_acceptor_rec* a, int64_t* t, uint32_t* b,
           uint32_t* nb, uint64_t* ms) {
   switch (pm) {
@@ -172,12 +172,7 @@ extern "C" int ev_host_run(const pxb_config* cfg, pxb_result* out, uint32_t* dig
   if (!cfg || !eligible(cfg)) return -1;
   const char* lv = getenv("EV_LAYOUT");                 // tests: force a layout
   const int layout = lv ? atoi(lv) : layout_for(cfg);
-  if (layout == 2 && cfg->delay_max > 8) return -1;
-  if ((layout == 3 || layout == 6 || layout == 7) && cfg->delay_max > 4) return -1;
-  if ((layout == 6 || layout == 7) && (cfg->loss_ppm || cfg->skew_max || (cfg->flags & PXB_CFG_RANDOMIZE) || cfg->n_ticks > 1)) return -1;
-  if ((layout == 4 || layout == 8 || layout == 9) != (cfg->n_ticks > 1)) return -1;   // log mode runs on the log-mode fields only
-  if (layout == 9 && cfg->delay_max > 4) return -1;
-  if ((layout == 0 || layout == 5) && cfg->delay_max > 8) return -1;
+  if (!layout_serves(layout, cfg)) return -1;
   // tests: the shape's proposer capacity; below n_proposers (fuzzed batches
   // only) it is the split routing of pxb_run_device, whose instances with more
   // proposers than the shape bail at init
@@ -188,16 +183,10 @@ extern "C" int ev_host_run(const pxb_config* cfg, pxb_result* out, uint32_t* dig
     if (pm > cfg->n_proposers || (pm < cfg->n_proposers && !(cfg->flags & PXB_CFG_RANDOMIZE))) return -1;
   }
   switch (layout) {
-    case 0: return run_w<8, false>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 1: return run_w<16, false>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 2: return run_w<8, true>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 3: return run_w<4, true>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 4: return run_w<8, false, true>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 5: return run_w<8, false, false, true>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 6: return run_w<4, true, false, false, 1>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 7: return run_w<4, true, false, false, 2>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 8: return run_w<16, false, true>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
-    case 9: return run_w<4, false, true, true>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
+#define PXB_EV_ROW(ID, W, C, L, S, SP, PART, BUILT) \
+  case ID: return run_w<W, C, L, S, SP>(cfg, pm, out, dig, acc, totals, bail_ids, n_bail, micro_steps);
+    PXB_EV_LAYOUTS(PXB_EV_ROW)
+#undef PXB_EV_ROW
   }
   return -1;
 }

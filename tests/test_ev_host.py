@@ -24,7 +24,7 @@ SRC = os.path.join(HERE, "native", "ev_host.cpp")
 DEFS = os.environ.get("PXB_EV_HOST_DEFS", "").split()
 OUT = os.path.join(HERE, "native", "_build", "libev_host%s.so" % ("".join(d.replace("-D", "_") for d in DEFS)))
 DEPS = [SRC] + [os.path.join(HERE, "..", "cloud-haskell-paxos_amd", "csrc", f)
-                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h")] + [os.path.join(HERE, "..", "include", "paxos_batch.h")]
+                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "ev_layouts.h")] + [os.path.join(HERE, "..", "include", "paxos_batch.h")]
 _lib = None
 
 
@@ -236,6 +236,27 @@ def test_split_shape_config5(first, monkeypatch):
     p3 = np.nonzero(drawn == 3)[0]
     assert set(p3.tolist()) <= set(bails.tolist())
     assert len(bails) - len(p3) <= 0.02 * 1500
+
+
+def test_split_shape_log_mode_randomized(monkeypatch):
+    """The first stage of fuzzed three-proposer log mode over three acceptors
+    (route_plan.h: the split routing's two-proposer shape on layout 4): exactly
+    the instances that drew P = 3 bail at init, the rest match the oracle.
+    A third of the instances draw P = 3 (1,500 draws: 500 +- 18, so under 0.39
+    at four deviations) and the log-mode shape's capacity bails stay under
+    0.05 (test_log_mode): max_bail_frac 0.45, as test_split_shape_config5's."""
+    monkeypatch.setenv("EV_PM", "2")
+    monkeypatch.setenv("EV_LAYOUT", "4")
+    cfg = pxb.Config(seed=0x7C3, n_proposers=3, n_acceptors=3, loss_ppm=200000, delay_max=3, skew_max=3,
+                     crash_ppm=100000, crash_len_max=12, crash_start_max=30, step_cap=1024, randomize=True,
+                     n_ticks=12, tick_period=5)
+    first, n = (1 << 32) - 700, 1500
+    drawn = np.array([paxos_ref.instance_params(cfg, first + g).P for g in range(n)])
+    p3 = np.nonzero(drawn == 3)[0]
+    assert 300 < len(p3) <= 0.39 * n
+    _, cnt, bails = check(cfg, first, n, max_bail_frac=0.45)
+    assert set(p3.tolist()) <= set(bails.tolist())
+    assert len(bails) - len(p3) <= 0.02 * n
 
 
 # ---- log mode (docs/SEMANTICS.md §9) on the per-lane state machine's log-mode

@@ -27,7 +27,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "ev_host.cpp")
 EXE = os.path.join(HERE, "native", "_build", "ev_host_san")
 DEPS = [SRC] + [os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
-                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h")] + \
+                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "ev_layouts.h")] + \
        [os.path.join(ROOT, "include", "paxos_batch.h")]
 FLAGS = ["--offload-arch=gfx950", "-O1", "-g0", "-std=c++17", "-DPXB_HOST_CHECKED", "-DPXB_EV_HOST_MAIN",
          "-DPXB_EV_HOST_FEW_N",

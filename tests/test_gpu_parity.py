@@ -973,7 +973,7 @@ def test_trace_production_variant_matches_oracle_steps(gpu_lib, c, inst):
 
 def test_log_mode_two_stage_routing(gpu_lib):
     """Faulty log mode over <= 10 links runs in two per-lane stages: the
-    log-mode shape (18-word pool) over the chunk, the same shape on the 16-step
+    log-mode shape (19-word pool) over the chunk, the same shape on the 16-step
     wheel with a 32-word pool over what it hands on, the general log-mode
     kernel over that one's.  A schedule whose responses pile up (delays to 8,
     no loss, a Tick every 2 steps: ~0.15 % stage-1 hand-offs, host model):
@@ -1016,6 +1016,30 @@ def test_log_mode_first_stage_layouts(gpu_lib):
         for x, y in zip(a[:3], b[:3]):
             assert np.array_equal(x, y)
         assert a[3] == b[3]
+
+
+@pytest.mark.parametrize("delay_max", [3, 6])
+def test_log_mode_randomized_three_proposers(gpu_lib, delay_max):
+    """Fuzzed three-proposer log mode over three acceptors is where the split
+    and the two-stage log-mode routings both apply; the split takes it
+    (route_plan.h: the two-proposer layout-4 shape over the chunk, the
+    three-proposer shape -- layout 9 with delays <= 4, else layout 4 -- over
+    the P = 3 instances it lists, the general log-mode kernel over that one's
+    bails).  Results, digests, acceptor records and totals equal the oracle's
+    and those of two-stage log mode (PXB_NO_SPLIT=1), of PXB_NO_LG2=1 (the
+    split again: it never depended on that switch), of the general kernel
+    alone (PXB_NO_EV=1) and of the id lists capped at 0 and 3 entries."""
+    cfg = pxb.Config(seed=0x7C3, n_proposers=3, n_acceptors=3, loss_ppm=200000, delay_max=delay_max, skew_max=3,
+                     crash_ppm=100000, step_cap=1024, randomize=True, n_ticks=12, tick_period=5)
+    first, n = (1 << 32) - 700, 4001
+    _cmp(cfg, first, n)
+    a = pxb.run(cfg, first, n, want_acceptors=True)
+    for env in ({"PXB_NO_SPLIT": "1"}, {"PXB_NO_LG2": "1"}, {"PXB_NO_EV": "1"}, {"PXB_EV_BAIL_CAP": "0"},
+                {"PXB_EV_BAIL_CAP": "3"}):
+        b = _with_env(env, lambda: pxb.run(cfg, first, n, want_acceptors=True))
+        for x, y in zip(a[:3], b[:3]):
+            assert np.array_equal(x, y), env
+        assert a[3] == b[3], env
 
 
 def test_log_mode_contiguous_faulty_config(gpu_lib):

@@ -26,7 +26,7 @@ SRC = os.path.join(HERE, "native", "trace_host.cpp")
 OUT = os.path.join(HERE, "native", "_build", "libtrace_host.so")
 EXE = os.path.join(HERE, "native", "_build", "trace_host_san")
 DEPS = [SRC] + [os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
-                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h")] + \
+                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h")] + \
        [os.path.join(ROOT, "include", "paxos_batch.h")]
 HIPCC = "/opt/rocm/bin/hipcc"
 U32 = 0xFFFFFFFF
