@@ -246,7 +246,10 @@ struct Hooks {
   // per-lane launch (the list and slot bookkeeping of the failure path);
   // PXB_FF1_BAIL=1 hands every fault-free instance to the general kernel
   bool fail_after_first, ff1_bail;
-  int blocks_per_cu;             // PXB_BLOCKS_PER_CU (0: none)
+  // A/B and tests: PXB_NO_WIN_PREPASS=1 keeps the per-lane kernels' window
+  // draws in their refill (no paxos_win.hip pre-pass)
+  bool no_win_prepass;
+  int blocks_per_cu;            // PXB_BLOCKS_PER_CU (0: none)
   int ff1_oversub, ffp_oversub;   // PXB_FF1_OVERSUB / PXB_FFP_OVERSUB (0: FF1_OVERSUB)
   char multi_fail_phase[16];      // PXB_MULTI_FAIL_PHASE / _DEVICE (paxos_multi.cpp)
   int multi_fail_device;
@@ -481,6 +484,7 @@ static void read_hooks_locked() {
   h.route.no_lgs = flag("PXB_NO_LGS");
   h.fail_after_first = flag("PXB_FAIL_AFTER_FIRST");
   h.ff1_bail = flag("PXB_FF1_BAIL");
+  h.no_win_prepass = flag("PXB_NO_WIN_PREPASS");
   h.route.bail_cap = num("PXB_EV_BAIL_CAP", -1);
   h.blocks_per_cu = std::max(0, num("PXB_BLOCKS_PER_CU", 0));
   const int fo = num("PXB_FF1_OVERSUB", 0), po = num("PXB_FFP_OVERSUB", 0);
@@ -795,8 +799,14 @@ int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_dig
     RecordOnExit list_use{lent ? lent->ev : nullptr, lent ? &lent->ev_set : nullptr, st};
     // a launch that fails after an earlier one of this chunk has queued leaves
     // the slot half used: zero it behind the queued work before reporting
+    // (and wait for that work: the queued per-lane kernel reads its windows
+    // from the caller's digest rows and writes its outputs there, and a caller
+    // that gets an error may free or reuse its buffers at once -- a next call
+    // into the same memory would find its rows overwritten under it.  The
+    // failure path only, so the wait under g_mu holds up nothing that matters.)
     auto fail = [&](hipError_t e) {
       (void)hipMemsetAsync(slot, 0, SLOT_U64 * sizeof(unsigned long long), st);
+      (void)hipStreamSynchronize(st);
       return hip_fail(e);
     };
     if (plan.kind == ROUTE_FF1 || plan.kind == ROUTE_FFP) {
@@ -835,6 +845,17 @@ int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_dig
       ek.bail_ids = bail;
       ek.bail_n = kp.queue + Q_BAIL;
       ek.bail_cap = plan.cap;
+      // The window pre-pass (paxos_win.hip): with a digest buffer, the chunk's
+      // isolation windows are drawn densely into its digest rows and every
+      // per-lane stage loads them in its refill.  A row keeps its windows until
+      // its instance finishes (a handed-on instance's is never written), so the
+      // second stage reads what this one pass left.  Without a digest buffer
+      // (totals-only runs), or when no instance can draw a window, the refill
+      // draws as before.  PXB_NO_WIN_PREPASS=1 turns it off.
+      if (kp.dig && !hk.no_win_prepass && (ek.p.cfg & (ev::EV_CFG_CRASHY | ev::EV_CFG_RANDOMIZE))) {
+        if (hipError_t e = ev::launch_windows(ek.p, N, (uint32_t)nc, kp.dig, st)) return fail(e);
+        ek.win = kp.dig;
+      }
       if (two_stage) {
         ev::EvKParams sk = ek;
         sk.bail_ids = slist;

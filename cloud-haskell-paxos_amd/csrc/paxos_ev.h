@@ -263,6 +263,40 @@ __host__ __device__ __forceinline__ uint32_t ctz32(uint32_t x) { return x ? (uin
 __host__ __device__ __forceinline__ uint32_t popc32(uint32_t x) { return (uint32_t)__builtin_popcount(x); }
 __host__ __device__ __forceinline__ uint32_t nbits32(uint32_t x) { return x ? 32u - (uint32_t)__builtin_clz(x) : 0u; }
 
+// the isolation window of an acceptor given its draw w (SEMANTICS §4):
+// c0 | c1 << 16, both clamped to 4096 (0: none)
+__host__ __device__ __forceinline__ uint32_t window_of(const EvParams& kp, const uint4& w, uint32_t crash_m1) {
+  uint32_t c0 = 0, c1 = 0;
+  if (w.x <= crash_m1) {
+    c0 = mulhi_n(w.y, kp.crash_start_max + 1u);
+    c1 = c0 + 1u + mulhi_n(w.z, kp.crash_len_max);
+  }
+  c0 = c0 < 4096u ? c0 : 4096u;
+  c1 = c1 < 4096u ? c1 : 4096u;
+  return c0 | (c1 << 16);
+}
+
+// Whether global instance `inst` draws isolation windows, and its crash
+// threshold - 1: the launch's, or (fuzzed batches) the instance's own, from
+// the same draw as EvLane::init takes it (SEMANTICS §4)
+__host__ __device__ __forceinline__ bool crash_of(const EvParams& kp, uint64_t inst, uint32_t& crash_m1) {
+  crash_m1 = kp.crash_m1;
+  if (!(kp.cfg & EV_CFG_RANDOMIZE)) return (kp.cfg & EV_CFG_CRASHY) != 0u;
+  const uint4 w = philox((uint32_t)inst, (uint32_t)(inst >> 32), 0u, 4u << 24, kp.k0, kp.k1);
+  const uint64_t ct = ev_threshold(mulhi_n(w.w, kp.crash_ppm + 1u));
+  crash_m1 = (uint32_t)(ct - 1ull);
+  return ct != 0ull;
+}
+
+// The word EvLane::init leaves in win[a] for global instance `inst`: what the
+// window pre-pass (paxos_win.hip) stores, one word per acceptor, for the
+// refill to load instead of drawing
+__host__ __device__ __forceinline__ uint32_t window_word(const EvParams& kp, uint64_t inst, uint32_t a, bool crashy,
+                                                         uint32_t crash_m1) {
+  if (!crashy) return 0u;
+  return window_of(kp, philox((uint32_t)inst, (uint32_t)(inst >> 32), 0u, (3u << 24) | a, kp.k0, kp.k1), crash_m1);
+}
+
 // Per-instance outcome handed to the driver when a lane finishes.
 struct EvOut {
   uint32_t res[4];                    // pxb_result
@@ -550,22 +584,18 @@ struct EvLane {
     return philox_rk(lo, hi, c2, c3, rk);
   }
 
-  // the isolation window of acceptor a of global instance (lo, hi) given its
-  // draw w (SEMANTICS §4): c0 | c1 << 16, both clamped to 4096 (0: none)
-  __host__ __device__ static __forceinline__ uint32_t window_of(const EvParams& kp, const uint4& w, uint32_t crash_m1) {
-    uint32_t c0 = 0, c1 = 0;
-    if (w.x <= crash_m1) {
-      c0 = mulhi_n(w.y, kp.crash_start_max + 1u);
-      c1 = c0 + 1u + mulhi_n(w.z, kp.crash_len_max);
-    }
-    c0 = c0 < 4096u ? c0 : 4096u;
-    c1 = c1 < 4096u ? c1 : 4096u;
-    return c0 | (c1 << 16);
-  }
-
   // ---- instance start: parameters, Tick skews, isolation windows (SEMANTICS §4) ----
-  __host__ __device__ __forceinline__ void init(const EvParams& kp, uint32_t g) {
+  // wsrc: the launch's pre-drawn windows, N words per instance (row g: the
+  // window pre-pass, paxos_win.hip), or null: draw them here.  Launch-uniform,
+  // so one scalar branch; the loads go first, so that the rest of init hides
+  // their latency.
+  __host__ __device__ __forceinline__ void init(const EvParams& kp, uint32_t g, const uint32_t* wsrc = nullptr) {
     gid = g;
+    if (wsrc) {
+      const uint32_t* const row = wsrc + (uint64_t)g * N;
+#pragma unroll
+      for (int a = 0; a < N; ++a) win[a] = row[a];
+    }
     const uint64_t inst = kp.first_instance + g;
     lo = (uint32_t)inst;
     hi = (uint32_t)(inst >> 32);
@@ -614,9 +644,12 @@ struct EvLane {
       refc[RPK ? 0 : p] = 0u;
       refp = 0u;
     }
+    if (!wsrc) {
+#pragma unroll
+      for (int a = 0; a < N; ++a) win[a] = crashy ? window_of(kp, draw(0u, (3u << 24) | (uint32_t)a), crash_m1) : 0u;
+    }
 #pragma unroll
     for (int a = 0; a < N; ++a) {
-      win[a] = crashy ? window_of(kp, draw(0u, (3u << 24) | (uint32_t)a), crash_m1) : 0u;
       accw[a] = 0u;
       if constexpr (LG) accv[a] = 0u;
       accd[a] = 0x811C9DC5u;

@@ -67,10 +67,20 @@ struct EvKParams {
   const uint32_t* ids;
   const uint32_t* n_ids;
   uint32_t ids_cap;
+  // optional: the instances' isolation windows, N words each at row gid, drawn
+  // by the window pre-pass (paxos_win.hip) into the digest rows (win == dig: a
+  // row holds its instance's windows until that instance finishes and its
+  // digests replace them; a handed-on instance's row keeps them for the next
+  // stage).  Null: every refill draws its own.
+  const uint32_t* win;
 #ifdef PXB_WAVE_TIMES
   unsigned long long* dbg;                    // diagnostic: per-wave (start, end, last grab, instances, HW_ID, XCC_ID)
 #endif
 };
+
+// the window pre-pass (paxos_win.hip): the window words of the `n` instances
+// from p.first_instance on, n_acc each, into rows[0 .. n * n_acc)
+hipError_t launch_windows(const EvParams& p, uint32_t n_acc, uint32_t n, uint32_t* rows, hipStream_t st);
 
 // response-pool words per lane of a shape (the compact layout is picked for
 // schedules with short delays, whose responses in flight stay fewer)
@@ -216,7 +226,10 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
   // several, and a lane ends every ~17 wave-iterations (config 4), so nearly
   // every refill started one lane; waiting for a second costs each instance
   // ~8 idle lane-iterations of its ~1090 (tools/wave_model.cpp refill_min):
-  // MI355X A/B, config 4 at 2^24: +1.3 %.  The refill test is taken only
+  // MI355X A/B, config 4 at 2^24: +1.3 %.  (With the windows loaded from the
+  // pre-pass's rows, kp.win, a refill is about half of that; a threshold of 1
+  // then measured the same as 2, 241.6-241.8 ms at 2^24 both: 2 stays.)
+  // The refill test is taken only
   // where the idle count changes (a refill leaves no idle lane unless the
   // chunk drained, so it clears the flag), and the steps in between run in an
   // inner loop whose back edge is one ballot (round 5: with the outputs stored
@@ -252,7 +265,7 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
         }
         const uint32_t take = min((uint32_t)__popcll(freeb), end - next);
         const uint32_t rank = (uint32_t)__popcll(freeb & below);
-        if (((freeb >> lane) & 1ull) && rank < take) L.init(kp.p, kp.n_ids ? kp.ids[next + rank] : next + rank);
+        if (((freeb >> lane) & 1ull) && rank < take) L.init(kp.p, kp.n_ids ? kp.ids[next + rank] : next + rank, kp.win);
         if (((freeb >> lane) & 1ull) && rank < take) {
           if (__builtin_expect(L.bailed, 0)) {   // (a fuzzed P above this shape's: the general kernel's)
             const uint32_t pos = atomicAdd(kp.bail_n, 1u);

@@ -169,7 +169,13 @@ int pxb_run(const pxb_config* cfg, pxb_result* out, uint32_t* log_digest,
  * event recorded behind the slot's previous chunk, so any number of chunks
  * may be in flight across streams (a 65th waits for the first's slot).  A
  * launch failure after a chunk's first kernel zeroes its slot (behind the
- * queued work) before the error is returned.                                 */
+ * queued work) and waits for that work before the error is returned, so
+ * nothing of a failed call still touches the caller's buffers.
+ * With a digest buffer, the faulty per-lane routings first draw every
+ * instance's isolation windows into its digest row (a dense pre-pass kernel);
+ * the row holds them until the instance finishes and its digests replace
+ * them.  The caller sees digests only, but while a call is in flight nothing
+ * else may write its digest buffer, not even the same values.               */
 int pxb_run_device(const pxb_config* cfg, pxb_result* d_out, uint32_t* d_log_digest,
                    pxb_acceptor_rec* d_acc, int64_t* d_totals, void* stream);
 
