@@ -304,12 +304,21 @@ struct EvOut {
   uint32_t steps;
 };
 
+// Where a lane's schedule draws come from (EvLane::draw): the default is the
+// Philox stream of (seed, instance id).  A source with kPhilox = false answers
+//   uint4 source_draw(lo, hi, c2, c3, rk)
+// itself (script_core.h: scripted schedules).  The source is a base class of
+// the lane, so the empty default adds nothing to it.
+struct PhiloxDraws {
+  static constexpr bool kPhilox = true;
+};
+
 // EARLY: a step may end with the copies of its last broadcast still to send
 // (see end_op); the trace kernel turns it off so that its per-step records
 // hold every message of the step in flight, as the oracle's do.
 template <int PM, int N, int POOL, int W, bool CMP, class Mem, bool EARLY = true, bool LG = false, bool SL = false,
-          int SP = 0>
-struct EvLane {
+          int SP = 0, class Src = PhiloxDraws>
+struct EvLane : Src {
   using S = Shape<PM, N, POOL, W, CMP, LG, SL, SP>;
   static constexpr bool kEarly = EARLY;
   // acceptor fields (Layouts): dead bit, log-length shift (LG: in accv) and its limit
@@ -581,7 +590,8 @@ struct EvLane {
     }
   }
   __host__ __device__ __forceinline__ uint4 draw(uint32_t c2, uint32_t c3) const {
-    return philox_rk(lo, hi, c2, c3, rk);
+    if constexpr (Src::kPhilox) return philox_rk(lo, hi, c2, c3, rk);
+    else return Src::source_draw(lo, hi, c2, c3, rk);
   }
 
   // ---- instance start: parameters, Tick skews, isolation windows (SEMANTICS §4) ----

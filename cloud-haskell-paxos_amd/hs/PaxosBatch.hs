@@ -40,6 +40,12 @@ module PaxosBatch
   , TraceSel (..)
   , allSteps
   , traceBatch
+    -- * Scripted schedules (the fault schedule as data: docs/SEMANTICS.md §10)
+  , ScriptRows
+  , scriptStride
+  , scheduleExtract
+  , runScripted
+  , traceScripted
     -- * Result queries (which instances to trace, without the results on the host)
   , Query (..)
   , FlagMode (..)
@@ -53,7 +59,7 @@ import           Control.Exception     (bracket_)
 import           Control.Monad         (forM)
 import           Data.Bits             (shiftR, testBit, (.&.))
 import           Data.Int              (Int32, Int64)
-import           Data.Word             (Word32, Word64)
+import           Data.Word             (Word16, Word32, Word64, Word8)
 import           Foreign.C.String      (CString, peekCString)
 import           Foreign.C.Types       (CInt (..))
 import           Foreign.ForeignPtr    (mallocForeignPtrArray, withForeignPtr)
@@ -160,6 +166,20 @@ foreign import ccall safe "pxb_trace_instance"
 foreign import ccall safe "pxb_trace_batch"
   c_pxb_trace_batch :: Ptr BatchConfig -> Ptr Word64 -> Word64 -> Ptr Word32 -> Ptr Word32 -> Word64 -> Ptr Word64
                     -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
+
+foreign import ccall unsafe "pxb_script_stride"
+  c_pxb_script_stride :: Word32 -> Word32 -> Word32 -> Word64
+
+foreign import ccall safe "pxb_schedule_extract"
+  c_pxb_schedule_extract :: Ptr BatchConfig -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word8 -> IO CInt
+
+foreign import ccall safe "pxb_run_scripted"
+  c_pxb_run_scripted :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Ptr Word32
+                     -> Ptr Word32 -> Ptr Word16 -> IO CInt
+
+foreign import ccall safe "pxb_trace_scripted"
+  c_pxb_trace_scripted :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Word64
+                       -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
 
 foreign import ccall safe "pxb_sweep"
   c_pxb_sweep :: Ptr BatchConfig -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64
@@ -365,6 +385,91 @@ traceBatch cfg ids sel = do
                     withForeignPtr buf $ \pb -> do
                       rc <- if total == 0 then pure 0
                             else c_pxb_trace_batch pc pids (fromIntegral n) psel pb total poff pst pres ptotal
+                      if rc /= 0
+                        then failed rc
+                        else do
+                          offs <- peekArray (n + 1) poff
+                          sts <- peekArray n pst
+                          Right <$> forM (zip3 [0 ..] (zip offs (drop 1 offs)) sts) (\(i, (o0, o1), st) ->
+                            if st /= 0
+                              then pure Nothing
+                              else do
+                                recs <- forM [fromIntegral o0 .. fromIntegral o1 - 1] $ \k ->
+                                  traceStep <$> peekArray nw (advancePtr pb (nw * k))
+                                [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                                pure (Just (recs, decode v t r f)))
+
+-- | Script rows as the C ABI lays them out (include/paxos_batch.h): @count@
+-- rows of 'scriptStride' bytes each, row-major.  A row is a Philox base id plus
+-- overrides of its schedule draws; 0xFF / 0xFFFF fields keep what Philox gives.
+type ScriptRows = [Word8]
+
+-- | pxb_script_stride: bytes between the rows of a call of @cfg@ at @depth@.
+scriptStride :: BatchConfig -> Word32 -> Int
+scriptStride cfg depth = fromIntegral (c_pxb_script_stride (bcProposers cfg) (bcAcceptors cfg) depth)
+
+-- | pxb_schedule_extract: the fully explicit rows of the schedule Philox gives
+-- (seed, id), no keep anywhere.
+-- (additive to ABI 5: a library without the symbol fails to link)
+scheduleExtract :: BatchConfig -> [Word64] -> Word32 -> IO (Either String ScriptRows)
+scheduleExtract cfg ids depth = do
+  let n = length ids
+      bytes = n * scriptStride cfg depth
+  with cfg $ \pc ->
+    withArray ids $ \pids ->
+      allocaArray (max 1 bytes) $ \prows -> do
+        rc <- c_pxb_schedule_extract pc pids (fromIntegral n) depth prows
+        if rc /= 0 then Left <$> (c_pxb_strerror rc >>= peekCString) else Right <$> peekArray bytes prows
+
+-- | pxb_run_scripted: @count@ rows through the per-lane state machine.  For
+-- every row: Nothing when its status is not OK (beyond the link capacities, or
+-- a malformed row), else its outcome and the messages sent on each link
+-- (@[dirn][p][a]@ flattened: the entries of the row the run consumed).
+runScripted :: BatchConfig -> ScriptRows -> Int -> Word32 -> IO (Either String [Maybe (Outcome, [Word16])])
+runScripted cfg rows n depth = do
+  let links = 2 * fromIntegral (bcProposers cfg) * fromIntegral (bcAcceptors cfg) :: Int
+  with cfg $ \pc ->
+    withArray rows $ \prows ->
+      allocaArray (max 1 (4 * n)) $ \pres ->
+        allocaArray (max 1 n) $ \pst ->
+          allocaArray (max 1 (links * n)) $ \psent -> do
+            rc <- c_pxb_run_scripted pc prows (fromIntegral n) depth pres nullPtr nullPtr pst psent
+            if rc /= 0
+              then Left <$> (c_pxb_strerror rc >>= peekCString)
+              else do
+                sts <- peekArray n pst
+                Right <$> forM (zip [0 ..] sts) (\(i, st) ->
+                  if st /= 0
+                    then pure Nothing
+                    else do
+                      [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                      sent <- peekArray links (advancePtr psent (links * i))
+                      pure (Just (decode v t r f, sent)))
+
+-- | pxb_trace_scripted: 'traceBatch' with script rows in place of ids (the
+-- default, end-of-step variant).
+traceScripted :: BatchConfig -> ScriptRows -> Int -> Word32 -> TraceSel
+              -> IO (Either String [Maybe ([TraceStep], Outcome)])
+traceScripted cfg rows n depth sel = do
+  let nw = 73                                      -- sizeof(pxb_trace_step) / 4
+      selw = [fst (selSteps sel), snd (selSteps sel), selTail sel, 0]
+      failed rc = Left <$> (c_pxb_strerror rc >>= peekCString)
+  with cfg $ \pc ->
+    withArray rows $ \prows ->
+      withArray selw $ \psel ->
+        allocaArray (n + 1) $ \poff ->
+          allocaArray (max 1 n) $ \pst ->
+            allocaArray (max 1 (4 * n)) $ \pres ->
+              allocaArray 1 $ \ptotal -> do
+                rc0 <- c_pxb_trace_scripted pc prows (fromIntegral n) depth psel nullPtr 0 poff pst pres ptotal
+                if rc0 /= 0
+                  then failed rc0
+                  else do
+                    [total] <- peekArray 1 ptotal
+                    buf <- mallocForeignPtrArray (max 1 (nw * fromIntegral total))
+                    withForeignPtr buf $ \pb -> do
+                      rc <- if total == 0 then pure 0
+                            else c_pxb_trace_scripted pc prows (fromIntegral n) depth psel pb total poff pst pres ptotal
                       if rc /= 0
                         then failed rc
                         else do

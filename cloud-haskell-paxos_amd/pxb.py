@@ -246,9 +246,19 @@ def load(path: str = LIB_PATH):
                        ("pxb_query_device", [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
                        ("pxb_sweep", [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
                        ("pxb_trace_batch_device", [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]),
-                       ("pxb_trace_batch", [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp])):
+                       ("pxb_trace_batch", [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_schedule_extract_device", [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+                       ("pxb_schedule_extract", [vp, vp, C.c_uint64, C.c_uint32, vp]),
+                       ("pxb_run_scripted_device", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+                       ("pxb_run_scripted", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]),
+                       ("pxb_trace_scripted_device",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_trace_scripted",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
+    lib.pxb_script_stride.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.pxb_script_stride.restype = C.c_uint64
     lib.pxb_stream_release.argtypes = [C.c_int, vp]
     lib.pxb_stream_release.restype = None
     lib.pxb_handoff_counts.argtypes = [C.c_int, vp, C.c_int]
@@ -587,6 +597,329 @@ def trace_batch_device(cfg: Config, d_ids, count: int, d_offsets, d_records=None
     s = C.c_void_p(stream) if stream else None
     check(lib.pxb_trace_batch_device(C.byref(c), _ptr(d_ids), count, C.byref(sel), _ptr(d_records) if capacity else None,
                                      capacity, _ptr(d_offsets), _ptr(d_status), _ptr(d_results), s))
+
+
+# ---- scripted schedules (include/paxos_batch.h, docs/SEMANTICS.md §10) --------
+SCRIPT_MAX_DEPTH = 4096
+SCRIPT_BAD = 2                   # status of a malformed row
+SCRIPT_KEEP8, SCRIPT_KEEP16 = 0xFF, 0xFFFF
+SCRIPT_HDR = 16
+
+
+def script_links_off(cfg: Config) -> int:
+    return SCRIPT_HDR + 4 * cfg.n_acceptors
+
+
+def script_stride(cfg: Config, depth: int) -> int:
+    """pxb_script_stride: bytes between the rows of a call (a multiple of 8)."""
+    return (script_links_off(cfg) + 2 * cfg.n_proposers * cfg.n_acceptors * depth + 7) & ~7
+
+
+def scripts_empty(cfg: Config, ids, depth: int):
+    """All-keep rows, uint8 (n, stride): row i is the instance ids[i]."""
+    import numpy as np
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    rows = np.zeros((len(ids), script_stride(cfg, depth)), dtype=np.uint8)
+    rows[:, 10:script_links_off(cfg) + 2 * cfg.n_proposers * cfg.n_acceptors * depth] = SCRIPT_KEEP8
+    script_base(rows)[:] = ids
+    return rows
+
+
+def _script_view(rows, off, dtype, tail):
+    """A numpy view (no copy) of a field of every row: shape (n,) + tail."""
+    import numpy as np
+    if rows.dtype != np.uint8 or rows.ndim != 2 or not rows.flags["C_CONTIGUOUS"]:
+        raise ValueError("rows: C-contiguous uint8 (n, stride) required")
+    size = np.dtype(dtype).itemsize
+    strides, s = [], size
+    for d in reversed(tail):
+        strides.insert(0, s)
+        s *= d
+    return np.ndarray((rows.shape[0],) + tuple(tail), dtype=dtype, buffer=rows, offset=off,
+                      strides=(rows.shape[1],) + tuple(strides))
+
+
+def script_base(rows):
+    """uint64 (n,): the Philox base ids."""
+    import numpy as np
+    return _script_view(rows, 0, np.uint64, ())
+
+
+def script_n_proposers(rows):
+    """uint8 (n,): 0 = keep, else the proposer count."""
+    import numpy as np
+    return _script_view(rows, 8, np.uint8, ())
+
+
+def script_skews(rows):
+    """uint16 (n, 3): the Tick steps, 0xFFFF = keep."""
+    import numpy as np
+    return _script_view(rows, 10, np.uint16, (3,))
+
+
+def script_windows(cfg: Config, rows):
+    """uint16 (n, N, 2): the isolation windows [c0, c1); both 0xFFFF = keep."""
+    import numpy as np
+    return _script_view(rows, SCRIPT_HDR, np.uint16, (cfg.n_acceptors, 2))
+
+
+def script_links(cfg: Config, rows, depth: int):
+    """uint8 (n, 2, P, N, depth): [dirn][p][a][k]; 0xFF keep, 0 lost, else the delay."""
+    import numpy as np
+    if rows.shape[1] != script_stride(cfg, depth):
+        raise ValueError("rows: stride %d, %d expected at depth %d" % (rows.shape[1], script_stride(cfg, depth), depth))
+    return _script_view(rows, script_links_off(cfg), np.uint8, (2, cfg.n_proposers, cfg.n_acceptors, depth))
+
+
+def _script_rows(cfg, rows, depth):
+    import numpy as np
+    if not 0 <= depth <= SCRIPT_MAX_DEPTH:
+        raise ValueError("depth: 0..%d" % SCRIPT_MAX_DEPTH)
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    if rows.ndim == 1:
+        rows = rows[None, :]
+    if rows.ndim != 2 or rows.shape[1] != script_stride(cfg, depth):
+        raise ValueError("rows: uint8 (n, %d) expected at depth %d" % (script_stride(cfg, depth), depth))
+    return rows
+
+
+def extract_schedule(cfg: Config, ids, depth: int):
+    """pxb_schedule_extract: the fully explicit rows (no keep anywhere) of the
+    schedule Philox gives (cfg.seed, ids[i]); uint8 (n, stride)."""
+    import numpy as np
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    rows = np.zeros((len(ids), script_stride(cfg, depth)), dtype=np.uint8)
+    c = cfg.to_c(0, 1)
+    n = len(ids)
+    check(load().pxb_schedule_extract(C.byref(c), _ptr(ids) if n else None, n, depth, _ptr(rows) if n else None))
+    return rows
+
+
+def run_scripted(cfg: Config, rows, depth: int, want_digests=True, want_acceptors=False):
+    """pxb_run_scripted: the rows through the per-lane state machine.  Returns
+    (results uint32 (n, 4), digests (n, N), acceptor records (n, N, 4), status
+    (n,), sent uint16 (n, 2, P, N)): pxb.run's outputs row by row, status
+    TRACE_OK / TRACE_BAILED / SCRIPT_BAD (not OK: zeroed outputs), and the
+    messages sent on every link (the entries of the row the run consumed)."""
+    import numpy as np
+    rows = _script_rows(cfg, rows, depth)
+    n, P, N = len(rows), cfg.n_proposers, cfg.n_acceptors
+    res = np.zeros((n, 4), dtype=np.uint32)
+    dig = np.zeros((n, N), dtype=np.uint32) if want_digests else None
+    acc = np.zeros((n, N, 4), dtype=np.uint32) if want_acceptors else None
+    status = np.zeros(n, dtype=np.uint32)
+    sent = np.zeros((n, 2, P, N), dtype=np.uint16)
+    c = cfg.to_c(0, 1)
+    if n:
+        check(load().pxb_run_scripted(C.byref(c), _ptr(rows), n, depth, _ptr(res), _ptr(dig), _ptr(acc), _ptr(status),
+                                      _ptr(sent)))
+    return res, dig, acc, status, sent
+
+
+def trace_scripted(cfg: Config, rows, depth: int, step_min: int = 0, step_max: int = U32_MAX, tail: int = 0,
+                   capacity=None):
+    """pxb_trace_scripted: trace_batch with script rows in place of ids (the
+    default variant only); the same returns."""
+    import numpy as np
+    lib = load()
+    rows = _script_rows(cfg, rows, depth)
+    n = len(rows)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint32)
+    res = np.zeros((n, 4), dtype=np.uint32)
+    c = cfg.to_c(0, 1)
+    sel = pxb_trace_sel(step_min, step_max, tail, 0)
+    total = C.c_uint64(0)
+    head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sel))
+    args = (_ptr(offs), _ptr(status) if n else None, _ptr(res) if n else None, C.byref(total))
+    if capacity is None:
+        check(lib.pxb_trace_scripted(*head, None, 0, *args))
+        capacity = total.value
+        if capacity == 0:
+            return np.zeros((0, TRACE_WORDS), dtype=np.uint32), offs, status, res
+    rec = np.zeros((capacity, TRACE_WORDS), dtype=np.uint32)
+    check(lib.pxb_trace_scripted(*head, _ptr(rec) if capacity else None, capacity, *args))
+    return rec[:min(total.value, capacity)], offs, status, res
+
+
+def _check_script_call(cfg, d_rows, count, depth):
+    if not 0 <= depth <= SCRIPT_MAX_DEPTH:
+        raise ValueError("depth: 0..%d" % SCRIPT_MAX_DEPTH)
+    if count > TRACE_BATCH_MAX:
+        raise ValueError("count: at most 2^30 rows a call")
+    if count and d_rows is None:
+        raise ValueError("d_rows is required")
+    if d_rows is not None:
+        _check_bytes("d_rows", d_rows, count * script_stride(cfg, depth))
+
+
+def extract_schedule_device(cfg: Config, d_ids, count: int, depth: int, d_rows, stream=None):
+    """pxb_schedule_extract_device on torch tensors, asynchronous on `stream`:
+    d_ids int64 (count,), d_rows uint8 (count * stride)."""
+    if count and d_ids is None:
+        raise ValueError("d_ids is required")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_ids", d_ids, count, 8)
+    c = cfg.to_c(0, 1)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_schedule_extract_device(C.byref(c), _ptr(d_ids), count, depth, _ptr(d_rows), s))
+
+
+def run_scripted_device(cfg: Config, d_rows, count: int, depth: int, d_results=None, d_digests=None,
+                        d_acceptors=None, d_status=None, d_sent=None, stream=None):
+    """pxb_run_scripted_device on torch tensors, asynchronous on `stream`: d_rows
+    uint8, d_results int32 (count, 4), d_digests int32 (count, N), d_acceptors
+    int32 (count, N, 4), d_status int32 (count,), d_sent int16 (count, 2, P, N);
+    every output optional.  Sizes and dtypes are checked here."""
+    N, P = cfg.n_acceptors, cfg.n_proposers
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    _check_buf("d_digests", d_digests, N * count, 4)
+    _check_buf("d_acceptors", d_acceptors, 4 * N * count, 4)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_sent", d_sent, 2 * P * N * count, 2)
+    c = cfg.to_c(0, 1)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_run_scripted_device(C.byref(c), _ptr(d_rows), count, depth, _ptr(d_results), _ptr(d_digests),
+                                         _ptr(d_acceptors), _ptr(d_status), _ptr(d_sent), s))
+
+
+def trace_scripted_device(cfg: Config, d_rows, count: int, depth: int, d_offsets, d_records=None, capacity: int = 0,
+                          d_status=None, d_results=None, step_min: int = 0, step_max: int = U32_MAX, tail: int = 0,
+                          stream=None):
+    """pxb_trace_scripted_device on torch tensors: trace_batch_device with d_rows
+    (uint8) and depth in place of d_ids."""
+    if d_offsets is None:
+        raise ValueError("d_offsets is required")
+    if capacity and d_records is None:
+        raise ValueError("d_records is required when capacity > 0")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_offsets", d_offsets, count + 1, 8)
+    _check_buf("d_records", d_records, TRACE_WORDS * capacity, 4)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    c = cfg.to_c(0, 1)
+    sel = pxb_trace_sel(step_min, step_max, tail, 0)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_trace_scripted_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sel),
+                                           _ptr(d_records) if capacity else None, capacity, _ptr(d_offsets),
+                                           _ptr(d_status), _ptr(d_results), s))
+
+
+# ---- the shrinker -------------------------------------------------------------
+def script_faults(cfg: Config, row, depth: int, sent):
+    """The faults of one explicit row given its run's send counts `sent`
+    (2, P, N): consumed link entries (k < sent) that are lost or delayed by more
+    than one step, ("link", dirn, p, a, k); non-zero skews of the proposers it
+    has, ("skew", p); non-empty windows, ("win", a)."""
+    row = _script_rows(cfg, row, depth)
+    P = int(script_n_proposers(row)[0]) or cfg.n_proposers
+    lk = script_links(cfg, row, depth)[0]
+    out = []
+    for p in range(P):
+        if script_skews(row)[0, p] not in (0, SCRIPT_KEEP16):
+            out.append(("skew", p))
+    for a in range(cfg.n_acceptors):
+        c0, c1 = (min(int(x), 4096) for x in script_windows(cfg, row)[0, a])
+        if c0 < c1:
+            out.append(("win", a))
+    for dirn in range(2):
+        for p in range(P):
+            for a in range(cfg.n_acceptors):
+                for k in range(min(int(sent[dirn, p, a]), depth)):
+                    b = int(lk[dirn, p, a, k])
+                    if b == 0 or (b != SCRIPT_KEEP8 and min(b, cfg.delay_max) > 1):
+                        out.append(("link", dirn, p, a, k))
+    return out
+
+
+def script_neutralise(cfg: Config, row, depth: int, fault):
+    """Neutralises one fault in place: a link entry := 1 (delivered next step),
+    a skew := 0, a window := none."""
+    row = row if row.ndim == 2 else row[None, :]
+    if fault[0] == "skew":
+        script_skews(row)[0, fault[1]] = 0
+    elif fault[0] == "win":
+        script_windows(cfg, row)[0, fault[1]] = 0
+    else:
+        script_links(cfg, row, depth)[(0,) + tuple(fault[1:])] = 1
+
+
+def _run_scripted_runner(cfg, rows, depth):
+    res, _, _, status, sent = run_scripted(cfg, rows, depth, want_digests=False)
+    return res, status, sent
+
+
+def shrink(cfg: Config, instance, flag_mask: int, runner=None, max_launches: int = 64, depth: int = 64):
+    """Reduces a failing instance to a 1-minimal set of faults.
+
+    `instance` is an instance id (its schedule is extracted on the GPU at
+    `depth`) or a fully explicit row (extract_schedule's).  The predicate is
+    (result.flags & flag_mask) != 0 with status TRACE_OK.  A fault is a consumed
+    link entry that is lost or delayed by more than one step, a non-zero skew or
+    a non-empty window (script_faults); neutralising sets it to 1, 0 or none.
+    Returns (row, faults, launches): the row is fully explicit with benign 1s
+    past what its run consumes, keeps the predicate under any seed and base, and
+    is 1-minimal (neutralising any one of `faults` loses the predicate) unless
+    the budget ran out first (launches + 2 > max_launches before a round).
+    A candidate whose run consumes more than `depth` entries on a link is
+    rejected like one that loses the predicate.  Rounds of two launches: every
+    single neutralisation of the current row, then every prefix of the
+    individually removable ones; the longest prefix that keeps the predicate is
+    taken.  `runner(cfg, rows, depth) -> (results, status, sent)` defaults to
+    run_scripted."""
+    import numpy as np
+    runner = runner or _run_scripted_runner
+    if isinstance(instance, (int, np.integer)):
+        row = extract_schedule(cfg, [int(instance)], depth)
+    else:
+        row = _script_rows(cfg, instance, depth).copy()
+    if len(row) != 1:
+        raise ValueError("instance: one id or one row")
+
+    def holds(res, status, sent):
+        return [bool(status[i] == TRACE_OK and (int(res[i][3]) & 0xFF & flag_mask) and int(sent[i].max()) <= depth)
+                for i in range(len(res))]
+
+    def settle(r, sent):
+        # benign 1s past what the run consumed (entries it never read)
+        lk = script_links(cfg, r, depth)[0]
+        k = np.arange(depth)[None, None, None, :]
+        lk[k >= np.asarray(sent, dtype=np.int64)[..., None]] = 1
+        nz = (lk != 0) & (lk != SCRIPT_KEEP8)
+        lk[nz] = np.minimum(lk[nz], cfg.delay_max)
+
+    res, status, sent = runner(cfg, row, depth)
+    launches = 1
+    if not holds(res, status, sent)[0]:
+        raise ValueError("shrink: the instance does not satisfy the predicate within depth %d" % depth)
+    sent = np.array(sent[0])
+    settle(row, sent)
+    while True:
+        faults = script_faults(cfg, row, depth, sent)
+        if not faults or launches + 2 > max_launches:
+            return row[0], faults, launches
+        cand = np.repeat(row, len(faults), axis=0)
+        for i, f in enumerate(faults):
+            script_neutralise(cfg, cand[i:i + 1], depth, f)
+        ok = holds(*runner(cfg, cand, depth))
+        launches += 1
+        removable = [f for f, o in zip(faults, ok) if o]
+        if not removable:
+            return row[0], faults, launches             # 1-minimal: this launch is the proof
+        cand = np.repeat(row, len(removable), axis=0)
+        for i in range(len(removable)):
+            for f in removable[:i + 1]:
+                script_neutralise(cfg, cand[i:i + 1], depth, f)
+        res, status, sent_c = runner(cfg, cand, depth)
+        launches += 1
+        ok = holds(res, status, sent_c)
+        best = max((i for i, o in enumerate(ok) if o), default=None)
+        if best is None:                                # (prefix 1 is launch 1's candidate: deterministic runs keep it)
+            raise PaxosError("shrink: a candidate that held did not hold again")
+        row = cand[best:best + 1].copy()
+        sent = np.array(sent_c[best])
+        settle(row, sent)
 
 
 def init(n_devices: int = 0):

@@ -499,6 +499,95 @@ int pxb_trace_batch(const pxb_config* cfg, const uint64_t* ids, uint64_t count, 
                     pxb_trace_step* records, uint64_t capacity, uint64_t* offsets,
                     uint32_t* status, pxb_result* results, uint64_t* n_records);
 
+/* ---- scripted schedules (additive to ABI 5, found by symbol like the queries) --
+ * The fault schedule as data (docs/SEMANTICS.md §10): a script ROW is one
+ * instance, a Philox base id plus overrides of its schedule draws.  Every field
+ * has a "keep" value that takes what Philox gives (cfg->seed, base), so a row of
+ * all "keep" is the instance `base`, and a fully explicit row (what
+ * pxb_schedule_extract writes) runs the same under any seed and base as long as
+ * no link consumes more than `depth` entries.
+ * For a call with P = cfg->n_proposers, N = cfg->n_acceptors and depth
+ * (0..PXB_SCRIPT_MAX_DEPTH), rows sit pxb_script_stride(P, N, depth) bytes apart
+ * (a multiple of 8; the rows are 8-byte aligned), little-endian:
+ *   offset  field
+ *   0       uint64 base            Philox counter id
+ *   8       uint8  n_proposers     0 = keep, else 1..P: overrides what
+ *                                  PXB_CFG_RANDOMIZE drew (or cfg->n_proposers)
+ *   9       uint8  reserved        must be 0
+ *   10      uint16 skew[3]         Tick step of proposer p; 0xFFFF = keep
+ *   16      N x {uint16 c0, c1}    isolation window [c0, c1) of acceptor a; both
+ *                                  0xFFFF = keep; c0 >= c1 = none; values clamp
+ *                                  to 4096 (steps are < 4095)
+ *   16+4N   uint8 link[2][P][N][depth]   [dirn][p][a][k]: the §4 message draw of
+ *                                  link (dirn, p, a) (dirn 0: p -> a, 1: a -> p),
+ *                                  seq k.  0xFF = keep, 0 = lost, 1..0xFE =
+ *                                  delivered with delay min(byte, cfg->delay_max)
+ *   ...     zero padding to the stride
+ * Seq k >= depth is always "keep".  A bad row (n_proposers > P, reserved != 0)
+ * gives status PXB_SCRIPT_BAD, a zeroed result and no records; its neighbours
+ * are unaffected.  An instance that outgrows the per-lane state machine's link
+ * capacities gives PXB_TRACE_BAILED, as in pxb_trace_batch: scripted runs never
+ * reach the general kernel.  cfg->first_instance and cfg->n_instances are
+ * ignored.  All three device calls are asynchronous on `stream` with no device
+ * synchronisation; the run and the trace launch one 64-lane wave per block
+ * (lane l of block b runs row 64 b + l), no block waits for another, and the
+ * trace takes its scratch (4 B per row + the scan's) from the per-device
+ * stream-ordered pool of the wire codec on that stream (the others need none).
+ * PXB_E_INVAL, before any device call, for a null cfg, null rows (ids, offsets)
+ * with count > 0, depth > PXB_SCRIPT_MAX_DEPTH, count > 2^30 and every config
+ * pxb_trace_instance rejects; the host forms return PXB_E_NODEV afterwards
+ * without a GPU.                                                              */
+#define PXB_SCRIPT_MAX_DEPTH 4096u
+#define PXB_SCRIPT_BAD       2u   /* status: malformed row (not run)            */
+#define PXB_SCRIPT_KEEP8     0xFFu
+#define PXB_SCRIPT_KEEP16    0xFFFFu
+/* the first 16 bytes of a row; the windows follow, then the link table */
+typedef struct pxb_script_head {
+  uint64_t base;
+  uint8_t  n_proposers;
+  uint8_t  reserved;
+  uint16_t skew[PXB_MAX_PROPOSERS];
+} pxb_script_head;
+typedef struct pxb_script_window { uint16_t c0, c1; } pxb_script_window;
+#define PXB_SCRIPT_WINDOWS_OFF    16u                        /* = sizeof(pxb_script_head) */
+#define PXB_SCRIPT_LINKS_OFF(n_acceptors) (16u + 4u * (n_acceptors))
+uint64_t pxb_script_stride(uint32_t n_proposers, uint32_t n_acceptors, uint32_t depth);
+
+/* pxb_schedule_extract: the schedule Philox gives (cfg->seed, ids[i]) as fully
+ * explicit rows, no "keep" anywhere: the drawn P (under PXB_CFG_RANDOMIZE), the
+ * skews, the windows (as window_of clamps them; none = 0, 0) and every link
+ * byte of the proposers the instance has.  Links of absent proposers are 0xFF
+ * (never read), their skews 0.  A dense kernel, one thread per row byte; pure
+ * Philox, no state machine runs.                                             */
+int pxb_schedule_extract_device(const pxb_config* cfg, const uint64_t* d_ids, uint64_t count, uint32_t depth,
+                                uint8_t* d_rows, void* stream);
+int pxb_schedule_extract(const pxb_config* cfg, const uint64_t* ids, uint64_t count, uint32_t depth, uint8_t* rows);
+
+/* pxb_run_scripted: the rows through the per-lane state machine; outputs as
+ * pxb_run's, row by row (d_out count results, d_log_digest and d_acc count * N;
+ * all nullable), d_status (nullable) PXB_TRACE_OK / PXB_TRACE_BAILED /
+ * PXB_SCRIPT_BAD (not OK: zeroed outputs), and d_sent (nullable, count x 2 P N
+ * uint16, link order as in the row): the messages sent on each link, i.e. the
+ * seqs consumed, which tell which entries mattered and whether depth covered
+ * the run.  No run totals: pxb_query_device works on d_out.                   */
+int pxb_run_scripted_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                            pxb_result* d_out, uint32_t* d_log_digest, pxb_acceptor_rec* d_acc,
+                            uint32_t* d_status, uint16_t* d_sent, void* stream);
+int pxb_run_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                     pxb_result* out, uint32_t* log_digest, pxb_acceptor_rec* acc, uint32_t* status,
+                     uint16_t* sent);
+
+/* pxb_trace_scripted: pxb_trace_batch with rows in place of ids: the same
+ * selection, offsets, capacity and sizing rules, and the same record bytes.
+ * The default (end-of-step) variant only: PXB_CFG_TRACE_PRODUCTION is
+ * PXB_E_INVAL.  Log mode as in pxb_trace_batch.                               */
+int pxb_trace_scripted_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                              const pxb_trace_sel* sel, pxb_trace_step* d_records, uint64_t capacity,
+                              uint64_t* d_offsets, uint32_t* d_status, pxb_result* d_results, void* stream);
+int pxb_trace_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                       const pxb_trace_sel* sel, pxb_trace_step* records, uint64_t capacity, uint64_t* offsets,
+                       uint32_t* status, pxb_result* results, uint64_t* n_records);
+
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
 int         pxb_last_hip_error(void);
