@@ -19,9 +19,7 @@
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
-#include "paxos_ev_kernel.h"
-#include "paxos_trace_core.h"
-#include "script_core.h"
+#include "script_lane.h"
 
 #ifndef PXB_SCR_P
 #error "PXB_SCR_P: the unit's proposer count (1, 2 or 3)"
@@ -58,9 +56,9 @@ scr_ptr scr_pick_p3(uint32_t n, int w, bool lg);
 // the shapes and pools of paxos_trace_batch_kernel's default variant
 template <int PM, int N, int W, bool LG = false>
 __global__ __launch_bounds__(64) void paxos_script_kernel(ScrParams k) {
-  constexpr int POOL = EvPool<PM, N, false, LG>::value;
-  using S = Shape<PM, N, POOL, W, false, LG>;
-  using Lane = EvLane<PM, N, POOL, W, false, LdsMem, false, LG, false, 0, ScriptDraws>;
+  using SL = ScriptLane<PM, N, W, LG, LdsMem, ScriptDraws>;
+  using S = typename SL::S;
+  using Lane = typename SL::Lane;
   __shared__ uint32_t lds[S::WORDS * 64];
   const uint32_t lane = threadIdx.x;
   const uint64_t i0 = (uint64_t)blockIdx.x * 64u, i = i0 + lane;
@@ -85,9 +83,7 @@ __global__ __launch_bounds__(64) void paxos_script_kernel(ScrParams k) {
       run = false;
     }
   }
-  while (any_lane(run)) {
-    if (run) run = T.iter(L, k.p);
-  }
+  script_run(L, T, k.p, run);
   if (!write && i < k.count) {
     if (k.cnt) k.cnt[i] = T.n;
     if (k.status) k.status[i] = T.status;

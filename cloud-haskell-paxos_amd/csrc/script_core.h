@@ -11,6 +11,10 @@
 //   (script_row_byte: the fully explicit row, one byte at a time);
 //   ScriptDraws, the draw source of a scripted lane (EvLane's Src), and
 //   script_begin / script_sent, the lane's start and its per-link send counts.
+// The draw and the start take what reads a link byte and what reads a skew or
+// a window as neutral as template parameters (source_draw_over,
+// script_begin_sel): the shrinker's candidates (shrink_core.h) are the same
+// lane over a row read through a rank table.
 //
 // The scripted lane leaves the state machine as it is: it runs with
 // lossy = true, loss_m1 = 0, dmax = 16 and no Tick-skew or window draws of its
@@ -134,13 +138,16 @@ struct ScriptDraws {
   uint32_t s_dmax, s_loss_m1;         // the instance's own thresholds (keep entries)
   bool s_lossy;
 
-  __host__ __device__ __forceinline__ uint4 source_draw(uint32_t lo, uint32_t hi, uint32_t c2, uint32_t c3,
-                                                        const uint32_t (&rk)[20]) const {
+  // the draw over `byte_at(index)`, what reads a link byte of the table (the
+  // shrinker's candidates read it beside their rank table: shrink_core.h)
+  template <class ByteAt>
+  __host__ __device__ __forceinline__ uint4 source_draw_over(uint32_t lo, uint32_t hi, uint32_t c2, uint32_t c3,
+                                                             const uint32_t (&rk)[20], const ByteAt& byte_at) const {
     if ((c3 >> 24) == 2u) return make_uint4(s_skew[0] << 16, s_skew[1] << 16, s_skew[2] << 16, 0u);
     const uint32_t dirn = (c3 >> 16) & 0xFFu, p = (c3 >> 8) & 0xFFu, a = c3 & 0xFFu, k = c2;
     const bool in = ((c3 >> 24) == 1u) & (dirn < 2u) & (p < s_P) & (a < s_N) & (k < s_depth);
     uint32_t b = SCR_KEEP8;
-    if (in) b = s_links[((uint64_t)((dirn * s_P + p) * s_N + a)) * s_depth + k];
+    if (in) b = byte_at(((uint64_t)((dirn * s_P + p) * s_N + a)) * s_depth + k);
     // an override: lost, or its delay clamped; keep: the real draw against the
     // instance's own thresholds.  The Philox rounds run for every entry, beside
     // the byte's load.  (Running them only for keep entries, a branch behind the
@@ -153,14 +160,27 @@ struct ScriptDraws {
     d = d < 1u ? 1u : (d > 15u ? 15u : d);         // (a lost message's delay is unused; PXB_MAX_DELAY = 15)
     return make_uint4(lost ? 0u : 1u, (d - 1u) << 28, 0u, 0u);
   }
+  struct RowByte {
+    const uint8_t* links;
+    __host__ __device__ __forceinline__ uint32_t operator()(uint64_t i) const { return links[i]; }
+  };
+  __host__ __device__ __forceinline__ uint4 source_draw(uint32_t lo, uint32_t hi, uint32_t c2, uint32_t c3,
+                                                        const uint32_t (&rk)[20]) const {
+    return source_draw_over(lo, hi, c2, c3, rk, RowByte{s_links});
+  }
 };
 
 // Starts the lane on `row` (L.m and L.set_keys(kp) done): PXB_TRACE_OK, or
 // PXB_SCRIPT_BAD for a malformed row (the lane is then not started).  P, N:
-// the call's; the lane's shape holds P proposers.
-template <class Lane>
-__host__ __device__ __forceinline__ uint32_t script_begin(Lane& L, const EvParams& kp, uint32_t depth,
-                                                          const uint8_t* row) {
+// the call's; the lane's shape holds P proposers.  `neutral(t)`: the skew of
+// proposer t (t < 3) or the window of acceptor t - 3 reads as 0 / none (the
+// shrinker's virtual candidates, shrink_core.h); script_begin: never.
+struct ScriptNoNeutral {
+  __host__ __device__ __forceinline__ bool operator()(uint32_t) const { return false; }
+};
+template <class Lane, class Neutral>
+__host__ __device__ __forceinline__ uint32_t script_begin_sel(Lane& L, const EvParams& kp, uint32_t depth,
+                                                              const uint8_t* row, const Neutral& neutral) {
   constexpr uint32_t P = Lane::S::PM, N = Lane::S::N;
   static_assert(!Lane::S::SP && !Lane::S::CMP && !Lane::S::SL, "the generic shape");
   const uint32_t lo = script_ld16(row, 0) | (script_ld16(row, 2) << 16);
@@ -168,7 +188,7 @@ __host__ __device__ __forceinline__ uint32_t script_begin(Lane& L, const EvParam
   const uint32_t np = row[8];
   if ((np > P) | (row[9] != 0u)) return PXB_SCRIPT_BAD;
   const ScriptInst si = script_inst(kp, lo, hi);
-  ScriptDraws& D = L;                 // (the lane's draw source: its base class)
+  ScriptDraws& D = L;                 // (the lane's draw source: its base class, or that one's)
   D.s_links = row + script_links_off(N);
   D.s_depth = depth;
   D.s_P = P;
@@ -180,7 +200,7 @@ __host__ __device__ __forceinline__ uint32_t script_begin(Lane& L, const EvParam
 #pragma unroll
   for (uint32_t p = 0; p < 3u; ++p) {
     const uint32_t v = script_ld16(row, 10u + 2u * p);
-    D.s_skew[p] = v == SCR_KEEP16 ? script_skew(kp, lo, hi, p) : v;
+    D.s_skew[p] = neutral(p) ? 0u : v == SCR_KEEP16 ? script_skew(kp, lo, hi, p) : v;
   }
   // the lane's own parameters: no draws of its own, synthetic thresholds
   EvParams pl = kp;
@@ -203,9 +223,14 @@ __host__ __device__ __forceinline__ uint32_t script_begin(Lane& L, const EvParam
       c1 = c1 < 4096u ? c1 : 4096u;
       wv = c0 >= c1 ? 0u : c0 | (c1 << 16);
     }
-    L.win[a] = wv;
+    L.win[a] = neutral(3u + a) ? 0u : wv;
   }
   return PXB_TRACE_OK;
+}
+template <class Lane>
+__host__ __device__ __forceinline__ uint32_t script_begin(Lane& L, const EvParams& kp, uint32_t depth,
+                                                          const uint8_t* row) {
+  return script_begin_sel(L, kp, depth, row, ScriptNoNeutral{});
 }
 
 // messages sent on each link of an ended instance (the seqs consumed), in the

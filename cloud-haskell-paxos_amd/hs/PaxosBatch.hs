@@ -46,6 +46,9 @@ module PaxosBatch
   , scheduleExtract
   , runScripted
   , traceScripted
+  , ShrinkStatus (..)
+  , Shrunk (..)
+  , shrinkBatch
     -- * Result queries (which instances to trace, without the results on the host)
   , Query (..)
   , FlagMode (..)
@@ -180,6 +183,10 @@ foreign import ccall safe "pxb_run_scripted"
 foreign import ccall safe "pxb_trace_scripted"
   c_pxb_trace_scripted :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Word64
                        -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
+
+foreign import ccall safe "pxb_shrink_batch"
+  c_pxb_shrink_batch :: Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Word32
+                     -> Ptr Word32 -> Ptr Word32 -> Ptr Word32 -> Ptr Word16 -> Ptr Word32 -> Ptr Word64 -> IO CInt
 
 foreign import ccall safe "pxb_sweep"
   c_pxb_sweep :: Ptr BatchConfig -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64
@@ -483,6 +490,58 @@ traceScripted cfg rows n depth sel = do
                                   traceStep <$> peekArray nw (advancePtr pb (nw * k))
                                 [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
                                 pure (Just (recs, decode v t r f)))
+
+-- | What 'shrinkBatch' says of one instance (PXB_SHRINK_*).
+data ShrinkStatus = ShrinkMinimal | ShrinkBudget | ShrinkNotInput | ShrinkTooMany | ShrinkUnstable
+  deriving (Show, Eq, Enum)
+
+-- | One instance of a 'shrinkBatch': its status, the faults left in its row,
+-- the launches it took part in, the row's send counts (@[dirn][p][a]@
+-- flattened) and outcome, and the signature of its minimal fault list (equal
+-- signatures: the same minimal schedule).
+data Shrunk = Shrunk
+  { shStatus    :: !ShrinkStatus
+  , shFaults    :: !Int
+  , shLaunches  :: !Int
+  , shSent      :: [Word16]
+  , shOutcome   :: Outcome
+  , shSignature :: !Word64
+  } deriving (Show, Eq)
+
+-- | pxb_shrink_batch: the schedules of @ids@ extracted at @depth@ and reduced to
+-- 1-minimal fault sets for the predicate (flags .&. mask /= 0), all at once on
+-- the device (docs/SEMANTICS.md §11); the shrunk rows and one 'Shrunk' each.
+-- (additive to ABI 5: a library without the symbol fails to link)
+shrinkBatch :: BatchConfig -> [Word64] -> Word32 -> Word32 -> Word32 -> IO (Either String (ScriptRows, [Shrunk]))
+shrinkBatch cfg ids depth mask maxLaunches = do
+  let n = length ids
+      bytes = n * scriptStride cfg depth
+      links = 2 * fromIntegral (bcProposers cfg) * fromIntegral (bcAcceptors cfg) :: Int
+  with cfg $ \pc ->
+    withArray ids $ \pids ->
+      allocaArray (max 1 bytes) $ \prows ->
+        allocaArray (max 1 n) $ \pst ->
+          allocaArray (max 1 n) $ \pnf ->
+            allocaArray (max 1 n) $ \pla ->
+              allocaArray (max 1 (links * n)) $ \psent ->
+                allocaArray (max 1 (4 * n)) $ \pres ->
+                  allocaArray (max 1 n) $ \psig -> do
+                    rc <- c_pxb_shrink_batch pc pids prows (fromIntegral n) depth mask maxLaunches
+                                             pst pnf pla psent pres psig
+                    if rc /= 0
+                      then Left <$> (c_pxb_strerror rc >>= peekCString)
+                      else do
+                        rows <- peekArray bytes prows
+                        sts <- peekArray n pst
+                        nfs <- peekArray n pnf
+                        las <- peekArray n pla
+                        sigs <- peekArray n psig
+                        out <- forM (zip [0 ..] (zip (zip sts nfs) (zip las sigs))) $ \(i, ((st, nf), (la, sg))) -> do
+                          [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                          sent <- peekArray links (advancePtr psent (links * i))
+                          pure (Shrunk (toEnum (fromIntegral (st :: Word32))) (fromIntegral (nf :: Word32))
+                                       (fromIntegral (la :: Word32)) sent (decode v t r f) sg)
+                        pure (Right (rows, out))
 
 -- | pxb_query.flag_mode: how (flags .&. mask) is tested.
 data FlagMode = AnyOf | AllOf | NoneOf

@@ -254,7 +254,11 @@ def load(path: str = LIB_PATH):
                        ("pxb_trace_scripted_device",
                         [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
                        ("pxb_trace_scripted",
-                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp])):
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_shrink_batch_device",
+                        [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+                       ("pxb_shrink_batch",
+                        [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
     lib.pxb_script_stride.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
@@ -920,6 +924,107 @@ def shrink(cfg: Config, instance, flag_mask: int, runner=None, max_launches: int
         row = cand[best:best + 1].copy()
         sent = np.array(sent_c[best])
         settle(row, sent)
+
+
+# ---- the batched shrinker (include/paxos_batch.h, docs/SEMANTICS.md §11) --------
+SHRINK_MINIMAL, SHRINK_BUDGET, SHRINK_NOT_INPUT, SHRINK_TOO_MANY, SHRINK_UNSTABLE = 0, 1, 2, 3, 4
+FNV64_BASIS, FNV64_PRIME = 0xCBF29CE484222325, 0x100000001B3
+
+
+def script_signature(cfg: Config, row, depth: int, sent) -> int:
+    """The signature pxb_shrink_batch gives a row: FNV-1a-64 over the row's
+    n_proposers byte, then 8 little-endian bytes per fault of script_faults(cfg,
+    row, depth, sent), in its order: skew (0, 0, p, 0, skew u16, 0 u16), window
+    (1, 0, 0, a, c0 u16, c1 u16; clamped to 4096), link (2, dirn, p, a, k u16,
+    byte u16)."""
+    import struct
+    row = _script_rows(cfg, row, depth)
+    data = bytes([int(script_n_proposers(row)[0])])
+    for f in script_faults(cfg, row, depth, sent):
+        if f[0] == "skew":
+            data += struct.pack("<4B2H", 0, 0, f[1], 0, int(script_skews(row)[0, f[1]]), 0)
+        elif f[0] == "win":
+            c0, c1 = (min(int(x), 4096) for x in script_windows(cfg, row)[0, f[1]])
+            data += struct.pack("<4B2H", 1, 0, 0, f[1], c0, c1)
+        else:
+            _, dirn, p, a, k = f
+            data += struct.pack("<4B2H", 2, dirn, p, a, k, int(script_links(cfg, row, depth)[0, dirn, p, a, k]))
+    h = FNV64_BASIS
+    for b in data:
+        h = ((h ^ b) * FNV64_PRIME) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def shrink_batch(cfg: Config, instances, flag_mask: int, depth: int = 64, max_launches: int = 64, chunk: int = 4096):
+    """pxb_shrink_batch: pxb.shrink for many instances at once, on the device.
+
+    `instances`: instance ids (1-D; their schedules are extracted on the GPU at
+    `depth`) or fully explicit rows (uint8 (n, stride)).  Runs in chunks of
+    `chunk` parents, so that the device scratch stays bounded.  Returns (rows
+    uint8 (n, stride), status (n,) SHRINK_*, n_faults (n,), launches (n,), sent
+    uint16 (n, 2, P, N), results uint32 (n, 4), signature uint64 (n,)): per
+    instance what shrink(cfg, instance, flag_mask, depth=depth,
+    max_launches=max_launches) returns, with a status where it raises."""
+    import numpy as np
+    if chunk < 1:
+        raise ValueError("chunk: at least 1")
+    if not 0 <= depth <= SCRIPT_MAX_DEPTH:
+        raise ValueError("depth: 0..%d" % SCRIPT_MAX_DEPTH)
+    inst = np.asarray(instances)
+    ids = None
+    if inst.ndim == 2:
+        rows = _script_rows(cfg, inst, depth).copy()
+    else:
+        ids = np.ascontiguousarray(inst, dtype=np.uint64).reshape(-1)
+        rows = np.zeros((len(ids), script_stride(cfg, depth)), dtype=np.uint8)
+    n, P, N = len(rows), cfg.n_proposers, cfg.n_acceptors
+    status = np.zeros(n, dtype=np.uint32)
+    n_faults = np.zeros(n, dtype=np.uint32)
+    launches = np.zeros(n, dtype=np.uint32)
+    sent = np.zeros((n, 2, P, N), dtype=np.uint16)
+    res = np.zeros((n, 4), dtype=np.uint32)
+    sig = np.zeros(n, dtype=np.uint64)
+    c = cfg.to_c(0, 1)
+    lib = load()
+    for a in range(0, n, chunk):
+        m = min(chunk, n - a)
+        check(lib.pxb_shrink_batch(C.byref(c), _ptr(ids[a:]) if ids is not None else None, _ptr(rows[a:]), m, depth,
+                                   flag_mask, max_launches, _ptr(status[a:]), _ptr(n_faults[a:]), _ptr(launches[a:]),
+                                   _ptr(sent[a:]), _ptr(res[a:]), _ptr(sig[a:])))
+    return rows, status, n_faults, launches, sent, res, sig
+
+
+def shrink_batch_device(cfg: Config, d_rows, count: int, depth: int, flag_mask: int, max_launches: int = 64,
+                        d_status=None, d_n_faults=None, d_launches=None, d_sent=None, d_results=None,
+                        d_signature=None, stream=None):
+    """pxb_shrink_batch_device on torch tensors: d_rows uint8 (count * stride),
+    shrunk in place; d_status, d_n_faults, d_launches int32 (count,), d_sent
+    int16 (count, 2, P, N), d_results int32 (count, 4), d_signature int64
+    (count,), every output optional.  Ordered on `stream`, which the call
+    synchronises once per launch."""
+    N, P = cfg.n_acceptors, cfg.n_proposers
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_n_faults", d_n_faults, count, 4)
+    _check_buf("d_launches", d_launches, count, 4)
+    _check_buf("d_sent", d_sent, 2 * P * N * count, 2)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    _check_buf("d_signature", d_signature, count, 8)
+    c = cfg.to_c(0, 1)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_shrink_batch_device(C.byref(c), _ptr(d_rows), count, depth, flag_mask, max_launches,
+                                         _ptr(d_status), _ptr(d_n_faults), _ptr(d_launches), _ptr(d_sent),
+                                         _ptr(d_results), _ptr(d_signature), s))
+
+
+def shrink_clusters(signature, status):
+    """The distinct minimal schedules of a shrink_batch: (signatures, counts)
+    over the rows with status MINIMAL or BUDGET, the largest cluster first."""
+    import numpy as np
+    signature, status = np.asarray(signature, dtype=np.uint64), np.asarray(status)
+    sig, cnt = np.unique(signature[(status == SHRINK_MINIMAL) | (status == SHRINK_BUDGET)], return_counts=True)
+    order = np.argsort(-cnt.astype(np.int64), kind="stable")
+    return sig[order], cnt[order]
 
 
 def init(n_devices: int = 0):

@@ -588,6 +588,67 @@ int pxb_trace_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t coun
                        const pxb_trace_sel* sel, pxb_trace_step* records, uint64_t capacity, uint64_t* offsets,
                        uint32_t* status, pxb_result* results, uint64_t* n_records);
 
+/* ---- batched shrinker (additive to ABI 5, found by symbol like the queries) ----
+ * Many failing schedules reduced to 1-minimal fault sets at once, everything on
+ * the device (docs/SEMANTICS.md §11).  Row i of d_rows (fully explicit rows, as
+ * pxb_schedule_extract writes them, pxb_script_stride apart) is shrunk in place.
+ * The PREDICATE of a run is: status PXB_TRACE_OK, result.flags & 0xFF &
+ * flag_mask != 0, and no link consumed more than `depth` entries.  A FAULT of a
+ * row, given its run's send counts, is a non-zero skew of a proposer the row
+ * has, a non-empty window, or a consumed link entry (k < min(sent, depth)) that
+ * is lost or delayed by more than one step; neutralising sets it to 0, none or
+ * 1.  Per row, launch 1 runs the row itself; then rounds of two launches while
+ * faults remain and launches + 2 <= max_launches: every single neutralisation
+ * (if none holds the row is 1-minimal: that launch is the proof), then every
+ * prefix of the removable faults, of which the longest that holds is taken
+ * with its send counts.  After every accepted row, link entries at k >= sent
+ * become 1 and the others that are neither 0 nor 0xFF are clamped to
+ * cfg->delay_max.  Rows run in lockstep and do not influence each other: a
+ * row's outputs do not depend on the batch, its position in it or repeats.
+ * Outputs (all nullable), per row:
+ *   d_status     PXB_SHRINK_*
+ *   d_n_faults   faults left in the returned row
+ *   d_launches   launches that row took part in (the initial one included)
+ *   d_sent       2 P N uint16, the returned row's send counts (link order)
+ *   d_results    the returned row's pxb_result (NOT_INPUT / TOO_MANY: the given row's)
+ *   d_signature  FNV-1a-64 (basis 0xCBF29CE484222325, prime 0x100000001B3) over the
+ *                row's n_proposers byte, then 8 bytes per fault in ascending
+ *                row offset, little-endian: skew (0, 0, p, 0, skew u16, 0 u16),
+ *                window (1, 0, 0, a, c0 u16, c1 u16; as clamped to 4096),
+ *                link (2, dirn, p, a, k u16, byte u16).  Equal signatures: the
+ *                same minimal schedule.
+ * NOT_INPUT and TOO_MANY leave the row as given, with launches 1, n_faults 0,
+ * sent and signature 0.
+ * No candidate row is ever stored: a candidate is its parent's row read through
+ * a uint16 rank table (one entry per skew, window and link byte), so scratch is
+ * count x (2 x stride + 2 x entries) plus, per launch, 1 B per candidate (and
+ * 4 P N + 16 B in the initial and prefix launches), all from the per-device
+ * stream-ordered pool on `stream`.  The rows are shrunk in a scratch copy and
+ * written back at the end: a call that fails (PXB_E_OOM for a failed
+ * allocation) has written nothing.  The host loop reads one 8-byte candidate
+ * total per launch to size the next grid, so the device form SYNCHRONISES ITS
+ * STREAM once per launch, at most 1 + 2 ceil((max_launches - 1) / 2) times.
+ * PXB_E_INVAL, before any device call, for a null cfg, null rows with count >
+ * 0, depth > PXB_SCRIPT_MAX_DEPTH, count > 2^30, flag_mask & 0xFF == 0,
+ * max_launches == 0, buffers misaligned for their element (rows 8, results
+ * 16), and every config pxb_trace_instance rejects.  count == 0 is valid.    */
+#define PXB_SHRINK_MINIMAL    0u   /* 1-minimal, or no faults at all                      */
+#define PXB_SHRINK_BUDGET     1u   /* stopped by max_launches: the last accepted row      */
+#define PXB_SHRINK_NOT_INPUT  2u   /* the given row does not hold the predicate           */
+#define PXB_SHRINK_TOO_MANY   3u   /* more than 65,534 faults: treated as NOT_INPUT       */
+#define PXB_SHRINK_UNSTABLE   4u   /* no prefix held (deterministic runs never give it)   */
+int pxb_shrink_batch_device(const pxb_config* cfg, uint8_t* d_rows, uint64_t count, uint32_t depth,
+                            uint32_t flag_mask, uint32_t max_launches,
+                            uint32_t* d_status, uint32_t* d_n_faults, uint32_t* d_launches,
+                            uint16_t* d_sent, pxb_result* d_results, uint64_t* d_signature, void* stream);
+/* pxb_shrink_batch: HOST buffers, blocking, on the current device; PXB_E_NODEV
+ * without a GPU (checked after the validation above).  ids non-null: rows is
+ * output only, the schedules of ids[i] are extracted on the device first.    */
+int pxb_shrink_batch(const pxb_config* cfg, const uint64_t* ids, uint8_t* rows, uint64_t count, uint32_t depth,
+                     uint32_t flag_mask, uint32_t max_launches,
+                     uint32_t* status, uint32_t* n_faults, uint32_t* launches,
+                     uint16_t* sent, pxb_result* results, uint64_t* signature);
+
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
 int         pxb_last_hip_error(void);
