@@ -254,6 +254,7 @@ struct Hooks {
   char multi_fail_phase[16];      // PXB_MULTI_FAIL_PHASE / _DEVICE (paxos_multi.cpp)
   int multi_fail_device;
   uint64_t sweep_chunk;           // PXB_SWEEP_CHUNK (instances per pxb_sweep chunk)
+  uint64_t explore_chunk;         // PXB_EXPLORE_CHUNK (candidates per pxb_explore chunk)
 };
 static Hooks g_hooks;
 static bool g_hooks_read = false;
@@ -495,6 +496,9 @@ static void read_hooks_locked() {
   h.multi_fail_device = num("PXB_MULTI_FAIL_DEVICE", -1);
   const char* sc = getenv("PXB_SWEEP_CHUNK");
   h.sweep_chunk = sc ? sweep_clamp_chunk(atoll(sc)) : SWEEP_CHUNK_DEFAULT;
+  const char* xc = getenv("PXB_EXPLORE_CHUNK");
+  const long long xv = xc ? atoll(xc) : 0;
+  h.explore_chunk = xv < 1 ? (1ull << 26) : xv > (1ll << 32) ? (1ull << 32) : (uint64_t)xv;   // (unset: 2^26)
   g_hooks = h;
   g_hooks_read = true;
 }
@@ -511,6 +515,8 @@ bool multi_fail_injected(const char* phase, int g) {
   const Hooks h = hooks();
   return h.multi_fail_phase[0] && strcmp(h.multi_fail_phase, phase) == 0 && h.multi_fail_device == g;
 }
+// (paxos_explore.hip's chunk size: candidates per pxb_explore chunk)
+uint64_t explore_chunk_hook(void) { return hooks().explore_chunk; }
 
 
 extern "C" void pxb_multi_release(void);   // paxos_multi.cpp

@@ -1,0 +1,438 @@
+// paxos_explore.hip — bounded exhaustive exploration (include/paxos_batch.h,
+// docs/SEMANTICS.md §12): pxb_explore, pxb_explore_device, pxb_explore_row and
+// pxb_explore_total.
+//
+// Every schedule within `radius` changed link entries of each parent row, run
+// on the device.  Candidate g of a call is candidate g % T of parent g / T (T is
+// the same for every parent: no search), and no candidate row exists: a
+// candidate is its parent's row read through ExploreByte (explore_core.h).
+// Four kernels and hipCUB's exclusive sum:
+//   the candidate kernel: paxos_shrink_kernel's shape over ExploreDraws.  Lane l
+//     of block b is candidate 64 b + l; it unranks its changes, tests its at
+//     most three site bytes for keep entries, runs to its end under TraceLane
+//     with the empty record window and writes ONE flag byte (ran OK, held);
+//   the minimal kernel, one thread per candidate: a held candidate ranks its at
+//     most 6 proper non-empty subsets and candidate 0, reads their bytes and
+//     sets the minimal bit; the wave adds its per-(parent, radius) counts with
+//     integer atomics (one add per distinct key and column); the block writes
+//     the number of candidates it lists;
+//   the cursor kernel and the scatter kernel of paxos_query.hip's list, over
+//     the flag bytes: ascending g from the caller's cursor, below `capacity`.
+// Everything is sized from count x T: the device form never synchronises.  No
+// block waits for another; plain vector stores only.
+//
+// Built as three units by proposer count (-DPXB_EXP_P=1|2|3), as
+// paxos_shrink.hip is; the unit of P = 1 also holds the other kernels and the
+// entry points.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "../../include/paxos_batch.h"
+#include "explore_core.h"
+#include "script_lane.h"
+
+#ifndef PXB_EXP_P
+#error "PXB_EXP_P: the unit's proposer count (1, 2 or 3)"
+#endif
+
+namespace pxb {
+namespace ev {
+
+struct ExpParams {
+  EvParams p;
+  ExploreSpace e;
+  const uint8_t* rows;              // the parents' rows
+  uint64_t stride;
+  uint64_t total;                   // candidates of this call (count * T <= 2^32)
+  uint32_t depth, site_depth, flag_mask;
+  uint8_t* bytes;                   // total flag bytes
+};
+
+typedef void (*exp_ptr)(ExpParams);
+// one per unit: the kernel of a shape (null: none)
+exp_ptr exp_pick_p1(uint32_t n, int w, bool lg);
+exp_ptr exp_pick_p2(uint32_t n, int w, bool lg);
+exp_ptr exp_pick_p3(uint32_t n, int w, bool lg);
+
+template <int PM, int N, int W, bool LG = false>
+__global__ __launch_bounds__(64) void paxos_explore_kernel(ExpParams k) {
+  using SL = ScriptLane<PM, N, W, LG, LdsMem, ExploreDraws>;
+  using S = typename SL::S;
+  using Lane = typename SL::Lane;
+  constexpr uint32_t NL = 2u * PM * N;
+  __shared__ uint32_t lds[S::WORDS * 64];
+  const uint32_t lane = threadIdx.x;
+  const uint64_t g = (uint64_t)blockIdx.x * 64u + lane;
+  Lane L;
+  L.m = LdsMem{lds, lane};
+  L.set_keys(k.p);
+  TraceLane<Lane> T;
+  T.begin_count(1u, 0u);            // (an empty window: no records are counted)
+  bool run = g < k.total;
+  if (run) {
+    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
+    const uint8_t* const row = k.rows + (uint64_t)i * k.stride;
+    const ExploreByte x = explore_byte(k.e, explore_unrank(k.e, c), row, N, k.site_depth, k.depth);
+    // a malformed parent runs nothing; a candidate that changes a keep site is skipped
+    run = !explore_parent_bad(row, PM) && !explore_changes_keep(x);
+    if (run) run = explore_begin(L, k.p, k.depth, row, x) == PXB_TRACE_OK;
+  }
+  const bool started = run;
+  script_run(L, T, k.p, run);
+  if (g < k.total) {
+    uint32_t f = 0u;
+    if (started && T.status == PXB_TRACE_OK) {
+      uint16_t snt[NL];
+      script_sent(L, snt);
+      f = explore_flags(T.status, T.res[3], snt, NL, k.depth, k.flag_mask);
+    }
+    k.bytes[g] = (uint8_t)f;
+  }
+}
+
+template <int PM, int W, bool LG = false>
+static exp_ptr pick_n(uint32_t n) {
+  switch (n) {
+    case 2: return paxos_explore_kernel<PM, 2, W, LG>;
+    case 3: return paxos_explore_kernel<PM, 3, W, LG>;
+    case 4: return paxos_explore_kernel<PM, 4, W, LG>;
+    case 5: return paxos_explore_kernel<PM, 5, W, LG>;
+    case 6: return paxos_explore_kernel<PM, 6, W, LG>;
+    case 7: return paxos_explore_kernel<PM, 7, W, LG>;
+    case 8: return paxos_explore_kernel<PM, 8, W, LG>;
+    case 9: return paxos_explore_kernel<PM, 9, W, LG>;
+  }
+  return nullptr;
+}
+
+// (log mode: the 8-step wheel only, as the script kernels)
+template <int PM>
+static exp_ptr pick_w(uint32_t n, int w, bool lg) {
+  if (lg) return w == 8 ? pick_n<PM, 8, true>(n) : nullptr;
+  return w == 8 ? pick_n<PM, 8>(n) : w == 16 ? pick_n<PM, 16>(n) : nullptr;
+}
+
+#if PXB_EXP_P == 1
+exp_ptr exp_pick_p1(uint32_t n, int w, bool lg) { return pick_w<1>(n, w, lg); }
+#elif PXB_EXP_P == 2
+exp_ptr exp_pick_p2(uint32_t n, int w, bool lg) { return pick_w<2>(n, w, lg); }
+#elif PXB_EXP_P == 3
+exp_ptr exp_pick_p3(uint32_t n, int w, bool lg) { return pick_w<3>(n, w, lg); }
+#else
+#error "PXB_EXP_P must be 1, 2 or 3"
+#endif
+
+}  // namespace ev
+}  // namespace pxb
+
+#if PXB_EXP_P == 1
+#include <hipcub/hipcub.hpp>
+
+namespace pxw {
+// paxos_wire.hip: per-call scratch from the device's stream-ordered pool
+int scratch(int dev, size_t bytes, hipStream_t st, void** p);
+}  // namespace pxw
+
+extern "C" uint64_t explore_chunk_hook(void);   // paxos_batch.hip: PXB_EXPLORE_CHUNK
+
+namespace pxx {
+using namespace pxb::ev;
+
+constexpr int XBLOCK = 256;                       // candidates per tile of the list (4 waves)
+constexpr int XWAVES = XBLOCK / 64;
+constexpr uint64_t MAX_PARENTS = 1ull << 30;
+constexpr uint64_t MAX_CALL = 1ull << 32;         // candidates of one device call
+
+struct ExpList {
+  ExploreSpace e;
+  const uint8_t* rows;
+  uint64_t stride;
+  uint64_t total;
+  uint32_t P;                       // the call's proposer count
+  uint32_t sel;                     // the listed bit: EXP_MINIMAL or EXP_HELD
+  uint8_t* bytes;
+  uint32_t* tcount;                 // listed candidates per tile
+  uint32_t* counts;                 // count * 4 * 3, zeroed (nullable)
+  uint32_t* status;                 // count (nullable)
+};
+
+__device__ __forceinline__ uint32_t block_sum(uint32_t wave_value, uint32_t* s_w) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  if (lane == 0u) s_w[w] = wave_value;
+  __syncthreads();
+  uint32_t t = 0u;
+#pragma unroll
+  for (int j = 0; j < XWAVES; ++j) t += s_w[j];
+  return t;
+}
+
+__global__ __launch_bounds__(XBLOCK) void explore_minimal_kernel(ExpList k) {
+  __shared__ uint32_t s_w[XWAVES];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t g = (uint64_t)blockIdx.x * XBLOCK + threadIdx.x;
+  const bool in = g < k.total;
+  uint32_t f = 0u, key = 0u;
+  if (in) {
+    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
+    key = i * 4u + explore_radius(k.e, c);
+    f = k.bytes[g];
+    // (the other candidates' held bits are final: this kernel only ever adds the minimal bit)
+    if ((f & EXP_HELD) && explore_is_minimal(k.e, explore_unrank(k.e, c), k.bytes + (uint64_t)i * tt)) {
+      f |= EXP_MINIMAL;
+      k.bytes[g] = (uint8_t)f;
+    }
+    if (c == 0u && k.status)
+      k.status[i] = explore_parent_bad(k.rows + (uint64_t)i * k.stride, k.P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
+  }
+  if (k.counts) {
+    // {ran OK, held, minimal} per (parent, radius): one add per distinct key of the wave and column
+    unsigned long long act = __ballot(f != 0u);
+    while (act != 0ull) {                         // (wave-uniform)
+      const int lead = __ffsll(act) - 1;
+      const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
+      const bool same = (f != 0u) & (key == k0);
+      const uint32_t n0 = (uint32_t)__popcll(__ballot(same & ((f & EXP_RAN) != 0u)));
+      const uint32_t n1 = (uint32_t)__popcll(__ballot(same & ((f & EXP_HELD) != 0u)));
+      const uint32_t n2 = (uint32_t)__popcll(__ballot(same & ((f & EXP_MINIMAL) != 0u)));
+      if ((int)lane == lead) {
+        uint32_t* const o = k.counts + (uint64_t)k0 * 3u;
+        if (n0) atomicAdd(o, n0);
+        if (n1) atomicAdd(o + 1, n1);
+        if (n2) atomicAdd(o + 2, n2);
+      }
+      act &= ~__ballot(same);
+    }
+  }
+  const uint32_t n = block_sum((uint32_t)__popcll(__ballot((f & k.sel) != 0u)), s_w);
+  if (threadIdx.x == 0u) k.tcount[blockIdx.x] = n;
+}
+
+// the list's base for this call = the caller's cursor; cursor += the call's matches
+__global__ void explore_cursor_kernel(uint64_t* __restrict__ cursor, const uint32_t* __restrict__ tcount,
+                                      const uint64_t* __restrict__ toff, uint64_t ntiles,
+                                      uint64_t* __restrict__ list_base) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint64_t b = *cursor;
+    *list_base = b;
+    *cursor = b + toff[ntiles - 1] + tcount[ntiles - 1];
+  }
+}
+
+__global__ __launch_bounds__(XBLOCK) void explore_scatter_kernel(const uint8_t* __restrict__ bytes, uint64_t total,
+                                                                 uint32_t sel, uint64_t first_g,
+                                                                 const uint32_t* __restrict__ tcount,
+                                                                 const uint64_t* __restrict__ toff,
+                                                                 const uint64_t* __restrict__ list_base,
+                                                                 uint64_t* __restrict__ ids, uint64_t capacity) {
+  __shared__ uint32_t s_w[XWAVES];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  // (both block-uniform) no listed candidate in the tile, or the list is full
+  if (tcount[blockIdx.x] == 0u) return;
+  const uint64_t pos = *list_base + toff[blockIdx.x];
+  if (pos >= capacity) return;
+  const uint64_t g = (uint64_t)blockIdx.x * XBLOCK + threadIdx.x;
+  const bool m = g < total && (bytes[g] & sel) != 0u;
+  const unsigned long long bal = __ballot(m);
+  if (lane == 0u) s_w[w] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t before = 0u;
+#pragma unroll
+  for (int j = 0; j < XWAVES; ++j) before += (j < (int)w) ? s_w[j] : 0u;
+  const uint64_t at = pos + before + (uint64_t)__popcll(bal & ((1ull << lane) - 1ull));
+  if (m && at < capacity) ids[at] = first_g + g;
+}
+
+struct Widen {
+  __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& c) const { return c; }
+};
+typedef hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> cnt_iter;
+
+static int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
+static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static int pick(const pxb_config* cfg, exp_ptr* fn) {
+  const bool lg = cfg->n_ticks > 1;
+  const int w = wheel_for(cfg->delay_max);
+  *fn = cfg->n_proposers == 1   ? exp_pick_p1(cfg->n_acceptors, w, lg)
+        : cfg->n_proposers == 2 ? exp_pick_p2(cfg->n_acceptors, w, lg)
+                                : exp_pick_p3(cfg->n_acceptors, w, lg);
+  return *fn ? PXB_OK : PXB_E_INVAL;
+}
+// the space of a call (T = 0: none)
+static ExploreSpace space_of(const pxb_config* cfg, uint32_t site_depth, uint32_t radius) {
+  return explore_space(explore_sites(cfg->n_proposers, cfg->n_acceptors, site_depth), cfg->delay_max, radius);
+}
+// the rules of a row's space: pxb_explore_row's, and part of the calls'
+static int validate_space(const pxb_config* cfg, uint32_t depth, const pxb_explore_space* sp, ExploreSpace* e) {
+  if (!cfg || !sp || depth > PXB_SCRIPT_MAX_DEPTH) return PXB_E_INVAL;
+  if (sp->site_depth == 0u || sp->site_depth > depth || sp->radius > PXB_EXPLORE_MAX_RADIUS) return PXB_E_INVAL;
+  if (!trace_config_ok(cfg)) return PXB_E_INVAL;
+  *e = space_of(cfg, sp->site_depth, sp->radius);
+  return e->T ? PXB_OK : PXB_E_INVAL;
+}
+// the argument rules both calls share
+static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,
+                    const pxb_explore_space* sp, const void* ids, uint64_t capacity, const void* n_matches,
+                    ExploreSpace* e, exp_ptr* fn) {
+  if (int rc = validate_space(cfg, depth, sp, e)) return rc;
+  if ((count && !rows) || count > MAX_PARENTS || !n_matches || (capacity && !ids)) return PXB_E_INVAL;
+  if ((sp->flag_mask & 0xFFu) == 0u || (sp->flags & ~PXB_EXPLORE_MINIMAL) != 0u) return PXB_E_INVAL;
+  return pick(cfg, fn);
+}
+static int device_count() {
+  int n = 0;
+  return (hipGetDeviceCount(&n) != hipSuccess) ? 0 : n;
+}
+
+}  // namespace pxx
+
+extern "C" {
+
+uint64_t pxb_explore_total(uint32_t P, uint32_t N, uint32_t delay_max, uint32_t site_depth, uint32_t radius) {
+  using namespace pxb::ev;
+  return explore_space(explore_sites(P, N, site_depth), delay_max, radius).T;
+}
+
+int pxb_explore_row(const pxb_config* cfg, uint32_t depth, const pxb_explore_space* space, const uint8_t* parent,
+                    uint64_t c, uint8_t* out_row) {
+  using namespace pxx;
+  ExploreSpace e;
+  if (int rc = validate_space(cfg, depth, space, &e)) return rc;
+  if (!parent || !out_row || c >= e.T) return PXB_E_INVAL;
+  const uint32_t N = cfg->n_acceptors;
+  const ExploreByte x = explore_byte(e, explore_unrank(e, c), parent, N, space->site_depth, depth);
+  if (explore_changes_keep(x)) return PXB_E_INVAL;
+  if (out_row != parent) memcpy(out_row, parent, (size_t)script_stride(cfg->n_proposers, N, depth));
+  uint8_t* const links = out_row + script_links_off(N);
+  for (uint32_t i = 0; i < 3u; ++i)
+    if (x.idx[i] != EXP_NO_SITE) links[x.idx[i]] = (uint8_t)explore_alt(x.links[x.idx[i]], x.dig[i], x.A);
+  return PXB_OK;
+}
+
+int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                       const pxb_explore_space* space, uint64_t first_parent, uint64_t* d_ids, uint64_t capacity,
+                       uint64_t* d_n_matches, uint32_t* d_counts, uint32_t* d_status, void* stream) {
+  using namespace pxx;
+  ExploreSpace e;
+  exp_ptr fn = nullptr;
+  if (int rc = validate(cfg, d_rows, count, depth, space, d_ids, capacity, d_n_matches, &e, &fn)) return rc;
+  if (count * e.T > MAX_CALL) return PXB_E_INVAL;                       // (count <= 2^30, T <= 2^30)
+  if (((uintptr_t)d_rows & 7u) || ((uintptr_t)d_ids & 7u) || ((uintptr_t)d_n_matches & 7u) ||
+      ((uintptr_t)d_counts & 3u) || ((uintptr_t)d_status & 3u))
+    return PXB_E_INVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (count == 0) return PXB_OK;
+
+  const uint64_t total = count * e.T, ntiles = (total + XBLOCK - 1) / XBLOCK;
+  size_t scan_b = 0;
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, cnt_iter(nullptr, Widen{}), (uint64_t*)nullptr,
+                                       (int64_t)ntiles, st) != hipSuccess)
+    return PXB_E_HIP;
+  // the call's scratch: list base | flag bytes | tile counts | tile offsets | scan
+  const size_t bytes_b = pad256((size_t)total), cnt_b = pad256((size_t)(ntiles * 4u)), off_b = pad256((size_t)(ntiles * 8u));
+  char* buf = nullptr;
+  if (int rc = pxw::scratch(dev, 256u + bytes_b + cnt_b + off_b + scan_b, st, reinterpret_cast<void**>(&buf)))
+    return rc;
+  uint64_t* const list_base = reinterpret_cast<uint64_t*>(buf);
+  uint8_t* const bytes = reinterpret_cast<uint8_t*>(buf + 256u);
+  uint32_t* const tcount = reinterpret_cast<uint32_t*>(buf + 256u + bytes_b);
+  uint64_t* const toff = reinterpret_cast<uint64_t*>(buf + 256u + bytes_b + cnt_b);
+  void* const scan_tmp = buf + 256u + bytes_b + cnt_b + off_b;
+
+  ExpParams c{};
+  c.p = make_params(cfg);
+  c.p.first_instance = 0;
+  c.e = e;
+  c.rows = d_rows;
+  c.stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
+  c.total = total;
+  c.depth = depth;
+  c.site_depth = space->site_depth;
+  c.flag_mask = space->flag_mask;
+  c.bytes = bytes;
+  ExpList l{};
+  l.e = e;
+  l.rows = d_rows;
+  l.stride = c.stride;
+  l.total = total;
+  l.P = cfg->n_proposers;
+  l.sel = (space->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
+  l.bytes = bytes;
+  l.tcount = tcount;
+  l.counts = d_counts;
+  l.status = d_status;
+
+  hipError_t err = hipSuccess;
+  do {
+    if (d_counts && (err = hipMemsetAsync(d_counts, 0, (size_t)(count * 12u * 4u), st)) != hipSuccess) break;
+    hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63u) / 64u)), dim3(64), 0, st, c);
+    if ((err = hipGetLastError()) != hipSuccess) break;
+    hipLaunchKernelGGL(explore_minimal_kernel, dim3((unsigned)ntiles), dim3(XBLOCK), 0, st, l);
+    if ((err = hipGetLastError()) != hipSuccess) break;
+    err = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, cnt_iter(tcount, Widen{}), toff, (int64_t)ntiles, st);
+    if (err != hipSuccess) break;
+    hipLaunchKernelGGL(explore_cursor_kernel, dim3(1), dim3(64), 0, st, d_n_matches, tcount, toff, ntiles, list_base);
+    if ((err = hipGetLastError()) != hipSuccess) break;
+    if (capacity) {
+      hipLaunchKernelGGL(explore_scatter_kernel, dim3((unsigned)ntiles), dim3(XBLOCK), 0, st, bytes, total, l.sel,
+                         first_parent * e.T, tcount, toff, list_base, d_ids, capacity);
+      err = hipGetLastError();
+    }
+  } while (0);
+  const hipError_t f = hipFreeAsync(buf, st);     // (stream-ordered: after the launches above)
+  if (err == hipSuccess) err = f;
+  return (err == hipSuccess) ? PXB_OK : hip_fail(err);
+}
+
+int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                const pxb_explore_space* space, uint64_t* ids, uint64_t capacity, uint64_t* n_matches,
+                uint32_t* counts, uint32_t* status) {
+  using namespace pxx;
+  ExploreSpace e;
+  exp_ptr fn = nullptr;
+  if (int rc = validate(cfg, rows, count, depth, space, ids, capacity, n_matches, &e, &fn)) return rc;
+  if (device_count() == 0) return PXB_E_NODEV;
+  *n_matches = 0;
+  if (count == 0) return PXB_OK;
+  // whole parents, at most PXB_EXPLORE_CHUNK candidates a chunk (and at least one parent)
+  const uint64_t chunk = explore_chunk_hook();
+  const uint64_t per = chunk / e.T ? chunk / e.T : 1u, m_max = per < count ? per : count;
+  const uint64_t stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
+  const uint64_t cap = capacity < count * e.T ? capacity : count * e.T;
+  const size_t rows_b = pad256((size_t)(m_max * stride)), ids_b = pad256((size_t)(cap * 8u));
+  const size_t cnt_b = pad256((size_t)(count * 48u)), st_b = pad256((size_t)(count * 4u));
+  char* buf = nullptr;                            // rows (one chunk) | cursor | ids | counts | status
+  hipError_t err = hipMalloc(&buf, rows_b + 256u + ids_b + cnt_b + st_b);
+  if (err != hipSuccess) return hip_fail(err);
+  uint8_t* const d_rows = reinterpret_cast<uint8_t*>(buf);
+  uint64_t* const d_n = reinterpret_cast<uint64_t*>(buf + rows_b);
+  uint64_t* const d_ids = reinterpret_cast<uint64_t*>(buf + rows_b + 256u);
+  uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(buf + rows_b + 256u + ids_b);
+  uint32_t* const d_st = reinterpret_cast<uint32_t*>(buf + rows_b + 256u + ids_b + cnt_b);
+  int rc = PXB_OK;
+  do {
+    if ((err = hipMemset(d_n, 0, 8u)) != hipSuccess) break;
+    for (uint64_t a = 0; a < count && rc == PXB_OK && err == hipSuccess; a += m_max) {
+      const uint64_t m = count - a < m_max ? count - a : m_max;
+      if ((err = hipMemcpy(d_rows, rows + a * stride, (size_t)(m * stride), hipMemcpyHostToDevice)) != hipSuccess) break;
+      rc = pxb_explore_device(cfg, d_rows, m, depth, space, a, cap ? d_ids : nullptr, cap, d_n,
+                              counts ? d_cnt + a * 12u : nullptr, status ? d_st + a : nullptr, nullptr);
+      // (the next chunk's rows overwrite these: wait for the kernels that read them)
+      if (rc == PXB_OK) err = hipStreamSynchronize(nullptr);
+    }
+    if (rc || err != hipSuccess) break;
+    if ((err = hipMemcpy(n_matches, d_n, 8u, hipMemcpyDeviceToHost)) != hipSuccess) break;
+    const uint64_t k = *n_matches < cap ? *n_matches : cap;
+    if (k && (err = hipMemcpy(ids, d_ids, (size_t)(k * 8u), hipMemcpyDeviceToHost)) != hipSuccess) break;
+    if (counts && (err = hipMemcpy(counts, d_cnt, (size_t)(count * 48u), hipMemcpyDeviceToHost)) != hipSuccess) break;
+    if (status && (err = hipMemcpy(status, d_st, (size_t)(count * 4u), hipMemcpyDeviceToHost)) != hipSuccess) break;
+    err = hipDeviceSynchronize();
+  } while (0);
+  (void)hipFree(buf);
+  return rc ? rc : (err == hipSuccess) ? PXB_OK : hip_fail(err);
+}
+
+}  // extern "C"
+#endif  // PXB_EXP_P == 1

@@ -49,6 +49,8 @@ module PaxosBatch
   , ShrinkStatus (..)
   , Shrunk (..)
   , shrinkBatch
+  , Explored (..)
+  , explore
     -- * Result queries (which instances to trace, without the results on the host)
   , Query (..)
   , FlagMode (..)
@@ -187,6 +189,10 @@ foreign import ccall safe "pxb_trace_scripted"
 foreign import ccall safe "pxb_shrink_batch"
   c_pxb_shrink_batch :: Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Word32
                      -> Ptr Word32 -> Ptr Word32 -> Ptr Word32 -> Ptr Word16 -> Ptr Word32 -> Ptr Word64 -> IO CInt
+
+foreign import ccall safe "pxb_explore"
+  c_pxb_explore :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word64 -> Word64
+                -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> IO CInt
 
 foreign import ccall safe "pxb_sweep"
   c_pxb_sweep :: Ptr BatchConfig -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64
@@ -542,6 +548,46 @@ shrinkBatch cfg ids depth mask maxLaunches = do
                           pure (Shrunk (toEnum (fromIntegral (st :: Word32))) (fromIntegral (nf :: Word32))
                                        (fromIntegral (la :: Word32)) sent (decode v t r f) sg)
                         pure (Right (rows, out))
+
+-- | One parent of an 'explore': whether its row was well formed, and for each
+-- radius 0..3 how many of its candidates (ran OK, held, are minimal).
+data Explored = Explored
+  { exOk     :: !Bool
+  , exCounts :: [(Int, Int, Int)]
+  } deriving (Show, Eq)
+
+-- | pxb_explore: every schedule within @radius@ (<= 3) changed link entries of
+-- each of the @n@ rows, the sites being the first @siteDepth@ entries of every
+-- link (docs/SEMANTICS.md §12).  Lists the candidates that hold the predicate
+-- (flags .&. mask /= 0), or with @minimal@ only those of which no proper subset
+-- of the changes holds, as @parent * T + c@ in ascending order, at most
+-- @capacity@ of them; with them the full match count and one 'Explored' a row.
+-- (additive to ABI 5: a library without the symbol fails to link)
+explore :: BatchConfig -> ScriptRows -> Int -> Word32 -> Word32 -> Word32 -> Word32 -> Bool -> Int
+        -> IO (Either String ([Word64], Word64, [Explored]))
+explore cfg rows n depth siteDepth radius mask minimal capacity =
+  with cfg $ \pc ->
+    withArray rows $ \prows ->
+      withArray [siteDepth, radius, mask, if minimal then 1 else 0] $ \pspace ->
+        allocaArray (max 1 capacity) $ \pids ->
+          allocaArray 1 $ \pn ->
+            allocaArray (max 1 (12 * n)) $ \pcnt ->
+              allocaArray (max 1 n) $ \pst -> do
+                rc <- c_pxb_explore pc prows (fromIntegral n) depth pspace
+                                    (if capacity > 0 then pids else nullPtr) (fromIntegral capacity) pn pcnt pst
+                if rc /= 0
+                  then Left <$> (c_pxb_strerror rc >>= peekCString)
+                  else do
+                    [total] <- peekArray 1 pn
+                    ids <- peekArray (min capacity (fromIntegral total)) pids
+                    sts <- peekArray n pst
+                    out <- forM (zip [0 ..] sts) $ \(i, st) -> do
+                      ws <- peekArray 12 (advancePtr pcnt (12 * i))
+                      let triple r = case map fromIntegral (take 3 (drop (3 * r) ws)) of
+                            [a, b, c] -> (a, b, c)
+                            _         -> (0, 0, 0)
+                      pure (Explored ((st :: Word32) == 0) (map triple [0 .. 3]))
+                    pure (Right (ids, total, out))
 
 -- | pxb_query.flag_mode: how (flags .&. mask) is tested.
 data FlagMode = AnyOf | AllOf | NoneOf

@@ -97,6 +97,12 @@ class pxb_trace_sel(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class pxb_explore_space(C.Structure):
+    _fields_ = [("site_depth", C.c_uint32), ("radius", C.c_uint32), ("flag_mask", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+assert C.sizeof(pxb_explore_space) == 16
 assert C.sizeof(pxb_config) == 72 and C.sizeof(pxb_result) == 16 and C.sizeof(pxb_trace_sel) == 16
 assert C.sizeof(pxb_acceptor_rec) == 16 and C.sizeof(pxb_msg) == 16
 assert C.sizeof(pxb_query) == 32
@@ -258,9 +264,15 @@ def load(path: str = LIB_PATH):
                        ("pxb_shrink_batch_device",
                         [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
                        ("pxb_shrink_batch",
-                        [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp])):
+                        [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+                       ("pxb_explore_row", [vp, C.c_uint32, vp, vp, C.c_uint64, vp]),
+                       ("pxb_explore_device",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_explore", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
+    lib.pxb_explore_total.argtypes = [C.c_uint32] * 5
+    lib.pxb_explore_total.restype = C.c_uint64
     lib.pxb_script_stride.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     lib.pxb_script_stride.restype = C.c_uint64
     lib.pxb_stream_release.argtypes = [C.c_int, vp]
@@ -1025,6 +1037,205 @@ def shrink_clusters(signature, status):
     sig, cnt = np.unique(signature[(status == SHRINK_MINIMAL) | (status == SHRINK_BUDGET)], return_counts=True)
     order = np.argsort(-cnt.astype(np.int64), kind="stable")
     return sig[order], cnt[order]
+
+
+# ---- exploration (include/paxos_batch.h, docs/SEMANTICS.md §12) ----------------
+EXPLORE_MAX_RADIUS = 3
+EXPLORE_MINIMAL = 1              # pxb_explore_space.flags: list only minimal candidates
+EXPLORE_MAX_TOTAL = 1 << 30
+
+
+def _explore_bases(S: int, A: int, radius: int):
+    """[base_0, .., base_(radius + 1)] of S sites with A alternatives each:
+    base_r = sum of C(S, q) A^q over q < r; the last is T."""
+    import math
+    base = [0]
+    for r in range(radius + 1):
+        base.append(base[-1] + math.comb(S, r) * A ** r)
+    return base
+
+
+def explore_total(cfg: Config, site_depth: int, radius: int) -> int:
+    """pxb_explore_total: the candidates per parent, or 0 for a space that is
+    invalid or larger than 2^30."""
+    P, N, A = cfg.n_proposers, cfg.n_acceptors, cfg.delay_max
+    if not (1 <= P <= 3 and 1 <= N <= 9 and 1 <= A <= 15 and 1 <= site_depth <= SCRIPT_MAX_DEPTH
+            and 0 <= radius <= EXPLORE_MAX_RADIUS):
+        return 0
+    T = _explore_bases(2 * P * N * site_depth, A, radius)[-1]
+    return T if T <= EXPLORE_MAX_TOTAL else 0
+
+
+def explore_unrank(S: int, A: int, radius: int, c: int):
+    """Candidate c of S sites with A alternatives within `radius`: (sites,
+    digits), the sites ascending.  With base_r <= c < base_(r+1) and x = c -
+    base_r, the sites satisfy x // A^r = sum of C(s_i, i) over i = 1..r (the
+    combinatorial number system) and site s_i takes digit (x % A^r // A^(i-1)) % A."""
+    import math
+    base = _explore_bases(S, A, radius)
+    if not 0 <= c < base[-1]:
+        raise ValueError("c: 0..%d" % (base[-1] - 1))
+    r = next(q for q in range(radius + 1) if c < base[q + 1])
+    m, v = divmod(c - base[r], A ** r)
+    sites, hi = [], S
+    for i in range(r, 0, -1):
+        lo, up = i - 1, hi                             # the largest s < hi with C(s, i) <= m
+        while up - lo > 1:
+            mid = (lo + up) // 2
+            lo, up = (mid, up) if math.comb(mid, i) <= m else (lo, mid)
+        sites.insert(0, lo)
+        m -= math.comb(lo, i)
+        hi = lo
+    return sites, [(v // A ** i) % A for i in range(r)]
+
+
+def explore_changes(cfg: Config, site_depth: int, radius: int, c: int):
+    """The changes of candidate c: [(dirn, p, a, k, digit)] in ascending site
+    order.  Site s is seq s % site_depth of link s // site_depth = (dirn P + p) N
+    + a; digit j of a site whose parent byte is b reads as (min(b, delay_max) + 1
+    + j) mod (delay_max + 1)."""
+    P, N = cfg.n_proposers, cfg.n_acceptors
+    if not explore_total(cfg, site_depth, radius):
+        raise ValueError("no such space (or more than 2^30 candidates)")
+    sites, digits = explore_unrank(2 * P * N * site_depth, cfg.delay_max, radius, c)
+    out = []
+    for s, j in zip(sites, digits):
+        link, k = divmod(s, site_depth)
+        out.append((link // N // P, link // N % P, link % N, k, j))
+    return out
+
+
+def _explore_unrank_many(S: int, A: int, radius: int, c):
+    """explore_unrank over an array: (r (n,), sites (n, 3), digits (n, 3)),
+    unused columns 0."""
+    import numpy as np
+    c = np.asarray(c, dtype=np.int64)
+    base = np.array(_explore_bases(S, A, radius), dtype=np.int64)
+    if len(c) and (c.min() < 0 or c.max() >= base[-1]):
+        raise ValueError("c: 0..%d" % (base[-1] - 1))
+    r = np.zeros(len(c), dtype=np.int64)
+    for q in range(1, radius + 1):
+        r[c >= base[q]] = q
+    apow = np.array([A ** q for q in range(4)], dtype=np.int64)
+    x = c - base[r]
+    m, v = x // apow[r], x % apow[r]
+    s = np.arange(S + 1, dtype=np.int64)
+    comb = [None, s, s * (s - 1) // 2, s * (s - 1) * (s - 2) // 6]
+    sites = np.zeros((len(c), 3), dtype=np.int64)
+    digits = np.zeros((len(c), 3), dtype=np.int64)
+    for q in range(1, radius + 1):                     # the candidates of radius q
+        w = np.nonzero(r == q)[0]
+        mq, hi = m[w], np.full(len(w), S, dtype=np.int64)
+        for i in range(q, 0, -1):
+            # the largest s < hi with C(s, i) <= m (C(., i) ascends; C(hi, i) > m by the recursion)
+            si = np.minimum(np.searchsorted(comb[i], mq, side="right") - 1, hi - 1)
+            sites[w, i - 1] = si
+            mq = mq - comb[i][si]
+            hi = si
+            digits[w, i - 1] = v[w] // apow[i - 1] % A
+    return r, sites, digits
+
+
+def _explore_apply(cfg, parents, depth, site_depth, radius, ids):
+    """(parent index, changed (n, 3) bool, link-table index (n, 3), new byte (n, 3),
+    keep (n, 3) bool) of the global candidate ids over `parents`."""
+    import numpy as np
+    parents = _script_rows(cfg, parents, depth)
+    if not 1 <= site_depth <= depth:
+        raise ValueError("site_depth: 1..depth")
+    T = explore_total(cfg, site_depth, radius)
+    if not T:
+        raise ValueError("no such space (or more than 2^30 candidates)")
+    ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1).astype(np.int64)
+    i, c = ids // T, ids % T
+    if len(ids) and i.max() >= len(parents):
+        raise ValueError("ids: beyond the last parent")
+    A = cfg.delay_max
+    r, sites, digits = _explore_unrank_many(2 * cfg.n_proposers * cfg.n_acceptors * site_depth, A, radius, c)
+    changed = np.arange(3)[None, :] < r[:, None]
+    idx = sites // site_depth * depth + sites % site_depth
+    b = parents[i[:, None], script_links_off(cfg) + idx].astype(np.int64)
+    new = (np.minimum(b, A) + 1 + digits) % (A + 1)
+    return parents, i, changed, idx, new, changed & (b == SCRIPT_KEEP8)
+
+
+def explore_skipped(cfg: Config, parents, depth: int, site_depth: int, radius: int, ids):
+    """bool (n,): the candidates that change a keep site (byte 0xFF) of their
+    parent.  They are skipped: not run, never "ran OK", never held."""
+    return _explore_apply(cfg, parents, depth, site_depth, radius, ids)[5].any(axis=1)
+
+
+def explore_rows(cfg: Config, parents, depth: int, site_depth: int, radius: int, ids):
+    """The candidates `ids` (global: parent index * T + c, as explore lists them)
+    of `parents` (one row or uint8 (n, stride)) materialised: uint8 (len(ids),
+    stride), what pxb_explore_row writes.  A candidate that changes a keep site
+    has no row: ValueError."""
+    import numpy as np
+    parents, i, changed, idx, new, keep = _explore_apply(cfg, parents, depth, site_depth, radius, ids)
+    if keep.any():
+        raise ValueError("ids: candidate %d changes a keep site" % int(np.asarray(ids).reshape(-1)[keep.any(axis=1)][0]))
+    rows = parents[i]
+    n, off = np.arange(len(rows)), script_links_off(cfg)
+    for j in range(3):
+        w = changed[:, j]
+        rows[n[w], off + idx[w, j]] = new[w, j]
+    return rows
+
+
+def explore(cfg: Config, parents, depth: int, site_depth: int, radius: int, flag_mask: int, minimal: bool = True,
+            capacity=None):
+    """pxb_explore: every schedule within `radius` changed sites of each parent
+    (the first site_depth entries of every link), run on the device.  Returns
+    (ids uint64 (k,), n_matches, counts uint32 (n, 4, 3), status uint32 (n,)):
+    the candidates that hold the predicate (`minimal`: those of which no proper
+    subset of the changes holds) as parent index * T + c, ascending, the first
+    `capacity` of them (None: all, at the price of a sizing run first);
+    counts[i, r] = (ran OK, held, minimal) of parent i at radius r; status
+    TRACE_OK or SCRIPT_BAD."""
+    import numpy as np
+    lib = load()
+    rows = _script_rows(cfg, parents, depth)
+    n = len(rows)
+    counts = np.zeros((n, 4, 3), dtype=np.uint32)
+    status = np.zeros(n, dtype=np.uint32)
+    c = cfg.to_c(0, 1)
+    sp = pxb_explore_space(site_depth, radius, flag_mask, EXPLORE_MINIMAL if minimal else 0)
+    nm = C.c_uint64(0)
+    head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sp))
+    tail = (C.byref(nm), _ptr(counts) if n else None, _ptr(status) if n else None)
+    if capacity is None:
+        check(lib.pxb_explore(*head, None, 0, *tail))
+        capacity = nm.value
+        if capacity == 0:
+            return np.zeros(0, dtype=np.uint64), 0, counts, status
+    ids = np.zeros(capacity, dtype=np.uint64)
+    check(lib.pxb_explore(*head, _ptr(ids) if capacity else None, capacity, *tail))
+    return ids[:min(nm.value, capacity)], nm.value, counts, status
+
+
+def explore_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int, radius: int, flag_mask: int,
+                   d_n_matches, d_ids=None, capacity: int = 0, d_counts=None, d_status=None, first_parent: int = 0,
+                   minimal: bool = True, stream=None):
+    """pxb_explore_device on torch tensors, asynchronous on `stream`, no
+    synchronisation: d_rows uint8 (count * stride); d_n_matches int64 (1,), the
+    write cursor, which has the call's full count added; d_ids int64 (capacity,)
+    takes (first_parent + i) * T + c, ascending; d_counts int32 (count, 4, 3)
+    and d_status int32 (count,) optional.  Sizes and dtypes are checked here."""
+    if d_n_matches is None:
+        raise ValueError("d_n_matches is required")
+    if capacity and d_ids is None:
+        raise ValueError("d_ids is required when capacity > 0")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_n_matches", d_n_matches, 1, 8)
+    _check_buf("d_ids", d_ids, capacity, 8)
+    _check_buf("d_counts", d_counts, 12 * count, 4)
+    _check_buf("d_status", d_status, count, 4)
+    c = cfg.to_c(0, 1)
+    sp = pxb_explore_space(site_depth, radius, flag_mask, EXPLORE_MINIMAL if minimal else 0)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_explore_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sp), first_parent,
+                                    _ptr(d_ids) if capacity else None, capacity, _ptr(d_n_matches), _ptr(d_counts),
+                                    _ptr(d_status), s))
 
 
 def init(n_devices: int = 0):

@@ -649,6 +649,86 @@ int pxb_shrink_batch(const pxb_config* cfg, const uint64_t* ids, uint8_t* rows, 
                      uint32_t* status, uint32_t* n_faults, uint32_t* launches,
                      uint16_t* sent, pxb_result* results, uint64_t* signature);
 
+/* ---- exploration (additive to ABI 5, found by symbol like the queries) ---------
+ * Every schedule within `radius` changed link entries of a row, run on the
+ * device (docs/SEMANTICS.md §12).  With P = cfg->n_proposers, N =
+ * cfg->n_acceptors and A = cfg->delay_max, the SITES of a row are the first
+ * site_depth entries of every link: S = 2 P N site_depth, site s = link
+ * s / site_depth (the row's link order, (dirn P + p) N + a), seq
+ * s % site_depth.  Skews and windows are not sites; a parent may carry any.
+ * Digit j (0..A-1) of a site whose parent byte is b reads as
+ * (min(b, A) + 1 + j) mod (A + 1): every value in 0..A (0: lost) but the
+ * parent's own.  With n_r = C(S, r) A^r and base_r the sum of n_q over q < r,
+ * a parent has T = base_(radius + 1) candidates; candidate c in [base_r,
+ * base_(r+1)), x = c - base_r, changes the r sites s_1 < .. < s_r with
+ * x / A^r = sum of C(s_i, i) (the combinatorial number system), site s_i taking
+ * digit (x % A^r / A^(i-1)) % A.  Candidate 0 is the parent itself.  A candidate
+ * that changes a site whose parent byte is 0xFF (keep; the links of absent
+ * proposers in extracted rows) is SKIPPED: it does not run, did not run OK and
+ * never holds.  A candidate HOLDS by the shrinker's predicate: status
+ * PXB_TRACE_OK, result.flags & 0xFF & flag_mask != 0 and no link consumed more
+ * than `depth` entries.  A held candidate is MINIMAL when no candidate made of
+ * a proper subset of its changes (same digits; candidate 0 included) holds.   */
+#define PXB_EXPLORE_MAX_RADIUS 3u
+#define PXB_EXPLORE_MINIMAL    1u   /* list only minimal candidates */
+typedef struct pxb_explore_space {  /* 16 B */
+  uint32_t site_depth;              /* 1..depth                                    */
+  uint32_t radius;                  /* 0..PXB_EXPLORE_MAX_RADIUS                   */
+  uint32_t flag_mask;               /* PXB_F_* bits of the predicate (& 0xFF != 0) */
+  uint32_t flags;                   /* PXB_EXPLORE_MINIMAL or 0                    */
+} pxb_explore_space;
+
+/* T, or 0 for a space that is invalid or larger than 2^30 candidates. */
+uint64_t pxb_explore_total(uint32_t n_proposers, uint32_t n_acceptors, uint32_t delay_max,
+                           uint32_t site_depth, uint32_t radius);
+
+/* pxb_explore_row: candidate c of `parent`, materialised into out_row
+ * (pxb_script_stride bytes; may be `parent` itself).  Host only, pure, never
+ * touches the GPU; space->flag_mask and flags are not read.  PXB_E_INVAL for
+ * c >= T, a changed keep site (nothing is written) and an invalid space.      */
+int pxb_explore_row(const pxb_config* cfg, uint32_t depth, const pxb_explore_space* space,
+                    const uint8_t* parent, uint64_t c, uint8_t* out_row);
+
+/* pxb_explore_device: DEVICE buffers, asynchronous on `stream`, no device
+ * synchronisation (everything is sized from count x T).  Runs the T candidates
+ * of each of the `count` rows of d_rows (pxb_script_stride apart, 8-byte
+ * aligned) and lists those that hold (space->flags & PXB_EXPLORE_MINIMAL: those
+ * that are minimal) as g = (first_parent + i) T + c, ascending in g.  Cursor and
+ * capacity as pxb_query_device's: *d_n_matches (required) is read as the write
+ * cursor and then has the call's full count added; matches at or past
+ * `capacity` are counted and not written, nothing at or past `capacity` entries
+ * is touched, and d_ids may be NULL only when capacity == 0.
+ *   d_counts (nullable)  count x 4 x 3 uint32, OVERWRITTEN: for each radius r in
+ *                        0..3, {ran OK, held, minimal} ("ran OK": status OK and
+ *                        within depth); 0 above `radius`.  The minimal column
+ *                        is always computed; integer adds: bit-reproducible.
+ *   d_status (nullable)  per parent PXB_TRACE_OK or PXB_SCRIPT_BAD; a bad parent
+ *                        runs nothing, lists nothing and has zero counts, and
+ *                        its neighbours are unaffected.
+ * No candidate row is ever stored: a candidate is its parent's row read through
+ * at most three (index, digit) pairs held in registers.  Scratch, from the
+ * per-device stream-ordered pool on `stream`: 1 B per candidate + 12 B per 256.
+ * PXB_E_INVAL, before any device call, for a null cfg, space or d_n_matches,
+ * null rows with count > 0, depth > PXB_SCRIPT_MAX_DEPTH, site_depth 0 or >
+ * depth, radius > 3, flag_mask & 0xFF == 0, unknown `flags` bits, T == 0,
+ * count > 2^30, count x T > 2^32, rows not 8-byte aligned (ids and cursor 8,
+ * counts and status 4), the d_ids rule above, and every config
+ * pxb_trace_instance rejects.  count == 0 is valid.                            */
+int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                       const pxb_explore_space* space, uint64_t first_parent,
+                       uint64_t* d_ids, uint64_t capacity, uint64_t* d_n_matches,
+                       uint32_t* d_counts, uint32_t* d_status, void* stream);
+/* pxb_explore: HOST buffers, blocking, on the current device; PXB_E_NODEV
+ * without a GPU (checked after the validation above; count x T is not bounded
+ * here).  *n_matches is OVERWRITTEN; first_parent is 0.  Walks the parents in
+ * chunks of whole parents, at most PXB_EXPLORE_CHUNK candidates a chunk (a test
+ * hook read like the others; default 2^26, clamped to [1, 2^32]) and at least
+ * one parent, so device memory is one chunk's rows and flag bytes plus the
+ * outputs (min(capacity, count x T) ids, the counts and the status).          */
+int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                const pxb_explore_space* space, uint64_t* ids, uint64_t capacity,
+                uint64_t* n_matches, uint32_t* counts, uint32_t* status);
+
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
 int         pxb_last_hip_error(void);

@@ -1,0 +1,259 @@
+// explore_host.cpp — TEST ONLY: the explorer's shared logic
+// (cloud-haskell-paxos_amd/csrc/explore_core.h: the space, unrank and rank,
+// ExploreByte and ExploreDraws over the per-lane state machine, the keep-site
+// test, the minimality test) driven sequentially on the host, one candidate at
+// a time, so tests/test_explore_host.py can check it against pxb.explore_rows
+// and the scripted lane without a GPU.  The product runs the same code on the
+// device (paxos_explore.hip); nothing here is linked into libpaxos_batch.so.
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../cloud-haskell-paxos_amd/csrc/explore_core.h"
+#include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
+
+using namespace pxb;
+using namespace pxb::ev;
+
+namespace {
+
+#define PXB_HCHK(c)                                                                                         \
+  do {                                                                                                     \
+    if (!(c)) {                                                                                            \
+      fprintf(stderr, "explore_host: LDS access out of the shape's words: %s (%s:%d)\n", #c, __FILE__, __LINE__); \
+      abort();                                                                                             \
+    }                                                                                                      \
+  } while (0)
+// one lane's words, every access checked against the shape's S::WORDS (as shrink_host.cpp's)
+struct HostMem {
+  uint32_t* w;
+  uint32_t n;
+  uint32_t ld(uint32_t i) const { PXB_HCHK(i < n); return w[i]; }
+  void st(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] = v; }
+  uint32_t ld16(uint32_t base, uint32_t i) const {
+    PXB_HCHK(2u * base + i < 2u * n);
+    return reinterpret_cast<const uint16_t*>(w + base)[i];
+  }
+  void st16(uint32_t base, uint32_t i, uint32_t v) const {
+    PXB_HCHK(2u * base + i < 2u * n);
+    reinterpret_cast<uint16_t*>(w + base)[i] = (uint16_t)v;
+  }
+  uint32_t ld16h(uint32_t i, uint32_t half) const {
+    PXB_HCHK(i < n && half < 2u);
+    return reinterpret_cast<const uint16_t*>(w + i)[half];
+  }
+  void st16h(uint32_t i, uint32_t half, uint32_t v) const {
+    PXB_HCHK(i < n && half < 2u);
+    reinterpret_cast<uint16_t*>(w + i)[half] = (uint16_t)v;
+  }
+  uint32_t ldh(uint32_t base, uint32_t i) const { return ld16(base, i); }
+  void sth(uint32_t base, uint32_t i, uint32_t v) const { st16(base, i, v); }
+  void orw(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] |= v; }
+};
+
+// one candidate: what one lane of paxos_explore_kernel does
+struct Cand {
+  const pxb_config* cfg;
+  const ExploreSpace* e;
+  const uint8_t* row;
+  uint32_t depth, site_depth, c, flag_mask;
+  uint8_t* flags;
+};
+
+template <int PM, int N, int W, bool LG>
+int run_shape(const Cand& a) {
+  using SL = ScriptLane<PM, N, W, LG, HostMem, ExploreDraws>;
+  using S = typename SL::S;
+  using Lane = typename SL::Lane;
+  constexpr uint32_t NL = 2u * PM * N;
+  *a.flags = 0u;
+  const ExploreByte x = explore_byte(*a.e, explore_unrank(*a.e, a.c), a.row, N, a.site_depth, a.depth);
+  if (explore_parent_bad(a.row, PM) || explore_changes_keep(x)) return 0;
+  std::vector<uint32_t> buf(S::WORDS, 0xDEADBEEFu);      // garbage: init must set what it reads
+  EvParams p = make_params(a.cfg);
+  p.first_instance = 0;
+  Lane L;
+  L.m = HostMem{buf.data(), (uint32_t)S::WORDS};
+  L.set_keys(p);
+  TraceLane<Lane> T;
+  const uint64_t guard_max = 100000ull * a.cfg->step_cap;   // a hang is a test failure
+  uint64_t guard = 0;
+  T.begin_count(1u, 0u);
+  if (explore_begin(L, p, a.depth, a.row, x) != PXB_TRACE_OK) return 0;
+  while (T.iter(L, p))
+    if (++guard > guard_max) return -100;
+  if (T.status != PXB_TRACE_OK) return 0;
+  uint16_t snt[NL];
+  script_sent(L, snt);
+  *a.flags = (uint8_t)explore_flags(T.status, T.res[3], snt, NL, a.depth, a.flag_mask);
+  return 0;
+}
+
+#ifdef PXB_EXPLORE_HOST_MAIN
+// (the sanitizer build: one shape, P = 1, N = 3 on the 8-step wheel)
+int dispatch(const Cand& a) {
+  const pxb_config* c = a.cfg;
+  if (c->n_proposers != 1 || c->n_acceptors != 3 || wheel_for(c->delay_max) != 8 || c->n_ticks > 1) return -1;
+  return run_shape<1, 3, 8, false>(a);
+}
+#else
+template <int PM, int W, bool LG>
+int run_n(const Cand& a) {
+  switch (a.cfg->n_acceptors) {
+    case 2: return run_shape<PM, 2, W, LG>(a);
+    case 3: return run_shape<PM, 3, W, LG>(a);
+    case 4: return run_shape<PM, 4, W, LG>(a);
+    case 5: return run_shape<PM, 5, W, LG>(a);
+    case 6: return run_shape<PM, 6, W, LG>(a);
+    case 7: return run_shape<PM, 7, W, LG>(a);
+    case 8: return run_shape<PM, 8, W, LG>(a);
+    case 9: return run_shape<PM, 9, W, LG>(a);
+  }
+  return -1;
+}
+template <int PM>
+int run_w(const Cand& a) {
+  const int w = wheel_for(a.cfg->delay_max);
+  if (a.cfg->n_ticks > 1) return w == 8 ? run_n<PM, 8, true>(a) : -1;
+  return w == 8 ? run_n<PM, 8, false>(a) : run_n<PM, 16, false>(a);
+}
+int dispatch(const Cand& a) {
+  switch (a.cfg->n_proposers) {
+    case 1: return run_w<1>(a);
+    case 2: return run_w<2>(a);
+    case 3: return run_w<3>(a);
+  }
+  return -1;
+}
+#endif
+
+}  // namespace
+
+extern "C" {
+
+// T of S sites with A alternatives within radius R (0: none)
+uint64_t explore_host_total(uint64_t S, uint32_t A, uint32_t R) { return explore_space(S, A, R).T; }
+
+// every candidate of the space: rank(unrank(c)) == c, the radius is that of c's
+// interval, the sites ascend below S, the digits are below A.  Returns the
+// number of candidates that fail (or ~0 for no space).
+uint64_t explore_host_check(uint64_t S, uint32_t A, uint32_t R) {
+  const ExploreSpace e = explore_space(S, A, R);
+  if (!e.T) return ~0ull;
+  uint64_t bad = 0;
+  for (uint64_t c = 0; c < e.T; ++c) {
+    const ExploreCand k = explore_unrank(e, c);
+    bool ok = k.r <= R && c >= e.base[k.r] && c < e.base[k.r + 1u] && explore_rank(e, k) == c;
+    for (uint32_t i = 0; i < k.r; ++i)
+      ok = ok && k.site[i] < S && (i == 0u || k.site[i - 1u] < k.site[i]) && k.digit[i] < A;
+    bad += !ok;
+  }
+  return bad;
+}
+
+// candidates c[0..n): out[7 i ..] = r, site[3], digit[3]
+int explore_host_unrank(uint64_t S, uint32_t A, uint32_t R, const uint64_t* c, uint64_t n, uint32_t* out) {
+  const ExploreSpace e = explore_space(S, A, R);
+  if (!e.T) return PXB_E_INVAL;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (c[i] >= e.T) return PXB_E_INVAL;
+    const ExploreCand k = explore_unrank(e, c[i]);
+    out[7 * i] = k.r;
+    for (uint32_t j = 0; j < 3u; ++j) out[7 * i + 1 + j] = k.site[j], out[7 * i + 4 + j] = k.digit[j];
+  }
+  return 0;
+}
+
+// pxb_explore_device on the host, its arguments; `bytes` (nullable): count * T
+// flag bytes, what the kernels keep in scratch
+int explore_host_run(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                     const pxb_explore_space* sp, uint64_t first_parent, uint64_t* ids, uint64_t capacity,
+                     uint64_t* n_matches, uint32_t* counts, uint32_t* status, uint8_t* bytes) {
+  if (!cfg || !sp || !n_matches || (count && !rows) || depth > PXB_SCRIPT_MAX_DEPTH || sp->site_depth == 0u ||
+      sp->site_depth > depth || sp->radius > PXB_EXPLORE_MAX_RADIUS || !(sp->flag_mask & 0xFFu) ||
+      (sp->flags & ~PXB_EXPLORE_MINIMAL) || (capacity && !ids) || !trace_config_ok(cfg))
+    return PXB_E_INVAL;
+  const uint32_t P = cfg->n_proposers, N = cfg->n_acceptors;
+  const ExploreSpace e = explore_space(explore_sites(P, N, sp->site_depth), cfg->delay_max, sp->radius);
+  if (!e.T || count * e.T > (1ull << 32)) return PXB_E_INVAL;
+  const uint64_t stride = script_stride(P, N, depth);
+  const uint32_t sel = (sp->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
+  uint64_t pos = *n_matches;
+  std::vector<uint8_t> f((size_t)e.T);
+  for (uint64_t i = 0; i < count; ++i) {
+    const uint8_t* const row = rows + i * stride;
+    for (uint64_t c = 0; c < e.T; ++c)
+      if (int rc = dispatch(Cand{cfg, &e, row, depth, sp->site_depth, (uint32_t)c, sp->flag_mask, &f[(size_t)c]}))
+        return rc;
+    uint32_t cnt[12] = {0u};
+    for (uint64_t c = 0; c < e.T; ++c) {
+      const ExploreCand k = explore_unrank(e, c);
+      if ((f[(size_t)c] & EXP_HELD) && explore_is_minimal(e, k, f.data())) f[(size_t)c] |= (uint8_t)EXP_MINIMAL;
+      for (uint32_t b = 0; b < 3u; ++b) cnt[k.r * 3u + b] += (f[(size_t)c] >> b) & 1u;
+      if (f[(size_t)c] & sel) {
+        if (pos < capacity) ids[pos] = (first_parent + i) * e.T + c;
+        ++pos;
+      }
+    }
+    if (counts) memcpy(counts + i * 12u, cnt, sizeof(cnt));
+    if (status) status[i] = explore_parent_bad(row, P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
+    if (bytes) memcpy(bytes + i * e.T, f.data(), (size_t)e.T);
+  }
+  *n_matches = pos;
+  return 0;
+}
+
+}  // extern "C"
+
+#ifdef PXB_EXPLORE_HOST_MAIN
+// Sanitizer-build driver (tests/test_explore_host.py): the benign row of P = 1,
+// N = 3, delay_max 2 (every link byte 1, no skews, no windows) explored at
+// depth 16, site_depth 2, radius 3, every buffer holding exactly what the call
+// may write.  To a file of raw bytes: the flag bytes, the counts, the status,
+// the match count and the listed ids.
+// argv: out seed step_cap flag_mask flags
+int main(int argc, char** argv) {
+  if (argc != 6) {
+    fprintf(stderr, "usage: %s out seed step_cap flag_mask flags\n", argv[0]);
+    return 2;
+  }
+  pxb_config c{};
+  c.seed = strtoull(argv[2], nullptr, 0);
+  c.n_proposers = 1;
+  c.n_acceptors = 3;
+  c.delay_max = 2;
+  c.n_ticks = 1;
+  c.tick_period = 1;
+  c.crash_len_max = 1;
+  c.step_cap = (uint32_t)strtoul(argv[3], nullptr, 0);
+  const pxb_explore_space sp{2u, 3u, (uint32_t)strtoul(argv[4], nullptr, 0), (uint32_t)strtoul(argv[5], nullptr, 0)};
+  const uint32_t depth = 16u;
+  const uint64_t T = explore_host_total(explore_sites(1u, 3u, sp.site_depth), c.delay_max, sp.radius);
+  std::vector<uint8_t> row((size_t)script_stride(1u, 3u, depth), 0u);   // exactly the row
+  row[8] = 1u;
+  memset(row.data() + script_links_off(3u), 1, (size_t)script_links_bytes(1u, 3u, depth));
+  std::vector<uint8_t> bytes((size_t)T);
+  std::vector<uint32_t> counts(12), status(1);
+  uint64_t n = 0;
+  if (explore_host_run(&c, row.data(), 1, depth, &sp, 0, nullptr, 0, &n, counts.data(), status.data(), bytes.data()))
+    return 4;
+  std::vector<uint64_t> ids((size_t)n);                                  // exactly the matches
+  uint64_t n2 = 0;
+  if (explore_host_run(&c, row.data(), 1, depth, &sp, 0, ids.data(), n, &n2, counts.data(), status.data(), bytes.data()) ||
+      n2 != n)
+    return 4;
+  FILE* o = fopen(argv[1], "wb");
+  if (!o) return 3;
+  fwrite(bytes.data(), 1, bytes.size(), o);
+  fwrite(counts.data(), 4, counts.size(), o);
+  fwrite(status.data(), 4, 1, o);
+  fwrite(&n, 8, 1, o);
+  fwrite(ids.data(), 8, ids.size(), o);
+  fclose(o);
+  return 0;
+}
+#endif
