@@ -21,14 +21,18 @@
 // Everything is sized from count x T: the device form never synchronises.  No
 // block waits for another; plain vector stores only.
 //
-// Built as three units by proposer count (-DPXB_EXP_P=1|2|3), as
-// paxos_shrink.hip is; the unit of P = 1 also holds the other kernels and the
-// entry points.
+// Built as three units by proposer count (-DPXB_EXP_P=1|2|3) so that the slow
+// device compiles overlap; the unit of P = 1 also holds the other kernels and
+// the entry points.  The shapes are lane_shapes.h's.  (The kernel spells out
+// what its lane does before and after the run, and tests/native/explore_host.cpp
+// spells it again: moved into shared members the same text compiled to other
+// register counts)
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
 #include "explore_core.h"
+#include "lane_shapes.h"
 #include "script_lane.h"
 
 #ifndef PXB_EXP_P
@@ -47,12 +51,6 @@ struct ExpParams {
   uint32_t depth, site_depth, flag_mask;
   uint8_t* bytes;                   // total flag bytes
 };
-
-typedef void (*exp_ptr)(ExpParams);
-// one per unit: the kernel of a shape (null: none)
-exp_ptr exp_pick_p1(uint32_t n, int w, bool lg);
-exp_ptr exp_pick_p2(uint32_t n, int w, bool lg);
-exp_ptr exp_pick_p3(uint32_t n, int w, bool lg);
 
 template <int PM, int N, int W, bool LG = false>
 __global__ __launch_bounds__(64) void paxos_explore_kernel(ExpParams k) {
@@ -90,57 +88,37 @@ __global__ __launch_bounds__(64) void paxos_explore_kernel(ExpParams k) {
   }
 }
 
-template <int PM, int W, bool LG = false>
-static exp_ptr pick_n(uint32_t n) {
-  switch (n) {
-    case 2: return paxos_explore_kernel<PM, 2, W, LG>;
-    case 3: return paxos_explore_kernel<PM, 3, W, LG>;
-    case 4: return paxos_explore_kernel<PM, 4, W, LG>;
-    case 5: return paxos_explore_kernel<PM, 5, W, LG>;
-    case 6: return paxos_explore_kernel<PM, 6, W, LG>;
-    case 7: return paxos_explore_kernel<PM, 7, W, LG>;
-    case 8: return paxos_explore_kernel<PM, 8, W, LG>;
-    case 9: return paxos_explore_kernel<PM, 9, W, LG>;
-  }
-  return nullptr;
-}
-
-// (log mode: the 8-step wheel only, as the script kernels)
+typedef void (*exp_ptr)(ExpParams);
+// the kernel of a config's shape among the unit's of PM proposers (null: none);
+// each unit specialises it for its own proposer count
 template <int PM>
-static exp_ptr pick_w(uint32_t n, int w, bool lg) {
-  if (lg) return w == 8 ? pick_n<PM, 8, true>(n) : nullptr;
-  return w == 8 ? pick_n<PM, 8>(n) : w == 16 ? pick_n<PM, 16>(n) : nullptr;
-}
+exp_ptr exp_pick(const pxb_config* cfg);
+template <> exp_ptr exp_pick<1>(const pxb_config* cfg);
+template <> exp_ptr exp_pick<2>(const pxb_config* cfg);
+template <> exp_ptr exp_pick<3>(const pxb_config* cfg);
 
-#if PXB_EXP_P == 1
-exp_ptr exp_pick_p1(uint32_t n, int w, bool lg) { return pick_w<1>(n, w, lg); }
-#elif PXB_EXP_P == 2
-exp_ptr exp_pick_p2(uint32_t n, int w, bool lg) { return pick_w<2>(n, w, lg); }
-#elif PXB_EXP_P == 3
-exp_ptr exp_pick_p3(uint32_t n, int w, bool lg) { return pick_w<3>(n, w, lg); }
-#else
-#error "PXB_EXP_P must be 1, 2 or 3"
-#endif
+template <int PM>
+struct ExpKernel {
+  template <int N, int W, bool LG>
+  exp_ptr shape() const { return paxos_explore_kernel<PM, N, W, LG>; }
+};
+template <>
+exp_ptr exp_pick<PXB_EXP_P>(const pxb_config* cfg) { return lane_shape(cfg, ExpKernel<PXB_EXP_P>{}, (exp_ptr) nullptr); }
 
 }  // namespace ev
 }  // namespace pxb
 
 #if PXB_EXP_P == 1
-#include <hipcub/hipcub.hpp>
-
-namespace pxw {
-// paxos_wire.hip: per-call scratch from the device's stream-ordered pool
-int scratch(int dev, size_t bytes, hipStream_t st, void** p);
-}  // namespace pxw
+#include "host_util.h"
 
 extern "C" uint64_t explore_chunk_hook(void);   // paxos_batch.hip: PXB_EXPLORE_CHUNK
 
 namespace pxx {
 using namespace pxb::ev;
+using namespace pxb::host;
 
 constexpr int XBLOCK = 256;                       // candidates per tile of the list (4 waves)
 constexpr int XWAVES = XBLOCK / 64;
-constexpr uint64_t MAX_PARENTS = 1ull << 30;
 constexpr uint64_t MAX_CALL = 1ull << 32;         // candidates of one device call
 
 struct ExpList {
@@ -242,20 +220,13 @@ __global__ __launch_bounds__(XBLOCK) void explore_scatter_kernel(const uint8_t* 
   if (m && at < capacity) ids[at] = first_g + g;
 }
 
-struct Widen {
-  __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& c) const { return c; }
+struct ExpPick {
+  const pxb_config* cfg;
+  template <int PM>
+  exp_ptr proposers() const { return exp_pick<PM>(cfg); }
 };
-typedef hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> cnt_iter;
-
-static int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
-static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int pick(const pxb_config* cfg, exp_ptr* fn) {
-  const bool lg = cfg->n_ticks > 1;
-  const int w = wheel_for(cfg->delay_max);
-  *fn = cfg->n_proposers == 1   ? exp_pick_p1(cfg->n_acceptors, w, lg)
-        : cfg->n_proposers == 2 ? exp_pick_p2(cfg->n_acceptors, w, lg)
-                                : exp_pick_p3(cfg->n_acceptors, w, lg);
+  *fn = lane_proposers(cfg, ExpPick{cfg}, (exp_ptr) nullptr);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 // the space of a call (T = 0: none)
@@ -275,13 +246,9 @@ static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uin
                     const pxb_explore_space* sp, const void* ids, uint64_t capacity, const void* n_matches,
                     ExploreSpace* e, exp_ptr* fn) {
   if (int rc = validate_space(cfg, depth, sp, e)) return rc;
-  if ((count && !rows) || count > MAX_PARENTS || !n_matches || (capacity && !ids)) return PXB_E_INVAL;
+  if ((count && !rows) || count > MAX_COUNT || !n_matches || (capacity && !ids)) return PXB_E_INVAL;
   if ((sp->flag_mask & 0xFFu) == 0u || (sp->flags & ~PXB_EXPLORE_MINIMAL) != 0u) return PXB_E_INVAL;
   return pick(cfg, fn);
-}
-static int device_count() {
-  int n = 0;
-  return (hipGetDeviceCount(&n) != hipSuccess) ? 0 : n;
 }
 
 }  // namespace pxx
@@ -322,12 +289,12 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
     return PXB_E_INVAL;
   const hipStream_t st = (hipStream_t)stream;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (int rc = current_device(&dev)) return rc;
   if (count == 0) return PXB_OK;
 
   const uint64_t total = count * e.T, ntiles = (total + XBLOCK - 1) / XBLOCK;
   size_t scan_b = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, cnt_iter(nullptr, Widen{}), (uint64_t*)nullptr,
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
                                        (int64_t)ntiles, st) != hipSuccess)
     return PXB_E_HIP;
   // the call's scratch: list base | flag bytes | tile counts | tile offsets | scan
@@ -371,7 +338,7 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
     if ((err = hipGetLastError()) != hipSuccess) break;
     hipLaunchKernelGGL(explore_minimal_kernel, dim3((unsigned)ntiles), dim3(XBLOCK), 0, st, l);
     if ((err = hipGetLastError()) != hipSuccess) break;
-    err = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, cnt_iter(tcount, Widen{}), toff, (int64_t)ntiles, st);
+    err = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, widen_iter(tcount, Widen{}), toff, (int64_t)ntiles, st);
     if (err != hipSuccess) break;
     hipLaunchKernelGGL(explore_cursor_kernel, dim3(1), dim3(64), 0, st, d_n_matches, tcount, toff, ntiles, list_base);
     if ((err = hipGetLastError()) != hipSuccess) break;

@@ -24,19 +24,14 @@
 // first matching lane's bin are counted with a ballot and added once, twice
 // over; what is left (values spread over many bins) goes in one by one.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <stdint.h>
 
 #include "../../include/paxos_batch.h"
-
-namespace pxw {
-// paxos_wire.hip: per-call scratch from the device's stream-ordered pool
-// (allocated and freed on the caller's stream; pxb_shutdown destroys the pool)
-int scratch(int dev, size_t bytes, hipStream_t st, void** p);
-}  // namespace pxw
+#include "host_util.h"
 
 namespace pxq {
+using namespace pxb::host;
 
 constexpr int QBLOCK = 512;                      // 8 waves
 constexpr int WAVES = QBLOCK / 64;
@@ -165,14 +160,6 @@ __global__ __launch_bounds__(QBLOCK) void scatter_kernel(const uint4* __restrict
   }
 }
 
-struct Widen {
-  __device__ __forceinline__ uint64_t operator()(const uint32_t& v) const { return v; }
-};
-
-int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
-
-size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace pxq
 
 using namespace pxq;
@@ -200,12 +187,12 @@ int pxb_query_device(const pxb_result* d_results, uint64_t first_instance, uint6
   if (count == 0) return PXB_OK;
   const hipStream_t st = (hipStream_t)stream;
   int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (int rc = current_device(&dev)) return rc;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return PXB_E_HIP;
 
   const uint64_t ntiles = (count + WTILE - 1) / WTILE;
   const uint64_t iters = (count + BTILE - 1) / BTILE;
-  hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> counts(nullptr, Widen{});
+  widen_iter counts(nullptr, Widen{});
   size_t need = 0;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, (uint64_t*)nullptr, (int64_t)ntiles, st) != hipSuccess)
     return PXB_E_HIP;
@@ -216,7 +203,7 @@ int pxb_query_device(const pxb_result* d_results, uint64_t first_instance, uint6
   uint32_t* tcount = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(buf) + 256);
   uint64_t* toff = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(buf) + 256 + cnt_b);
   void* tmp = reinterpret_cast<char*>(buf) + 256 + cnt_b + off_b;
-  counts = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>(tcount, Widen{});
+  counts = widen_iter(tcount, Widen{});
 
   const uint32_t nb = (q->n_bins_steps > q->n_bins_rounds) ? q->n_bins_steps : q->n_bins_rounds;
   // resident blocks: 4 per CU by waves, 2 with both full histograms in LDS (64 KiB a block)

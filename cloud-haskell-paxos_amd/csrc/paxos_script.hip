@@ -13,12 +13,17 @@
 //
 // The extract is a dense kernel over the rows' bytes: pure Philox.
 //
-// Built as three units by proposer count (-DPXB_SCR_P=1|2|3), as
-// paxos_trace_batch.hip is; the unit of P = 1 also holds the entry points.
+// Built as three units by proposer count (-DPXB_SCR_P=1|2|3) so that the slow
+// device compiles overlap; the unit of P = 1 also holds the entry points.  The
+// shapes are lane_shapes.h's.  (The kernel spells out what its lane does before
+// and after the run, and tests/native/script_host.cpp spells it again: moved into
+// shared members, as the trace batch's is, the same text compiled to another
+// register allocation and ran 2 - 3 % slower)
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "lane_shapes.h"
 #include "script_lane.h"
 
 #ifndef PXB_SCR_P
@@ -46,12 +51,6 @@ struct ScrParams {
   uint4* acc;                       // count * N acceptor records
   uint16_t* sent;                   // count * 2 P N
 };
-
-typedef void (*scr_ptr)(ScrParams);
-// one per unit: the kernel of a shape (null: none)
-scr_ptr scr_pick_p1(uint32_t n, int w, bool lg);
-scr_ptr scr_pick_p2(uint32_t n, int w, bool lg);
-scr_ptr scr_pick_p3(uint32_t n, int w, bool lg);
 
 // the shapes and pools of paxos_trace_batch_kernel's default variant
 template <int PM, int N, int W, bool LG = false>
@@ -113,54 +112,32 @@ __global__ __launch_bounds__(64) void paxos_script_kernel(ScrParams k) {
   }
 }
 
-template <int PM, int W, bool LG = false>
-static scr_ptr pick_n(uint32_t n) {
-  switch (n) {
-    case 2: return paxos_script_kernel<PM, 2, W, LG>;
-    case 3: return paxos_script_kernel<PM, 3, W, LG>;
-    case 4: return paxos_script_kernel<PM, 4, W, LG>;
-    case 5: return paxos_script_kernel<PM, 5, W, LG>;
-    case 6: return paxos_script_kernel<PM, 6, W, LG>;
-    case 7: return paxos_script_kernel<PM, 7, W, LG>;
-    case 8: return paxos_script_kernel<PM, 8, W, LG>;
-    case 9: return paxos_script_kernel<PM, 9, W, LG>;
-  }
-  return nullptr;
-}
-
-// (log mode: the 8-step wheel only, as the batch kernels' LG shape)
+typedef void (*scr_ptr)(ScrParams);
+// the kernel of a config's shape among the unit's of PM proposers (null: none);
+// each unit specialises it for its own proposer count
 template <int PM>
-static scr_ptr pick_w(uint32_t n, int w, bool lg) {
-  if (lg) return w == 8 ? pick_n<PM, 8, true>(n) : nullptr;
-  return w == 8 ? pick_n<PM, 8>(n) : w == 16 ? pick_n<PM, 16>(n) : nullptr;
-}
+scr_ptr scr_pick(const pxb_config* cfg);
+template <> scr_ptr scr_pick<1>(const pxb_config* cfg);
+template <> scr_ptr scr_pick<2>(const pxb_config* cfg);
+template <> scr_ptr scr_pick<3>(const pxb_config* cfg);
 
-#if PXB_SCR_P == 1
-scr_ptr scr_pick_p1(uint32_t n, int w, bool lg) { return pick_w<1>(n, w, lg); }
-#elif PXB_SCR_P == 2
-scr_ptr scr_pick_p2(uint32_t n, int w, bool lg) { return pick_w<2>(n, w, lg); }
-#elif PXB_SCR_P == 3
-scr_ptr scr_pick_p3(uint32_t n, int w, bool lg) { return pick_w<3>(n, w, lg); }
-#else
-#error "PXB_SCR_P must be 1, 2 or 3"
-#endif
+template <int PM>
+struct ScrKernel {
+  template <int N, int W, bool LG>
+  scr_ptr shape() const { return paxos_script_kernel<PM, N, W, LG>; }
+};
+template <>
+scr_ptr scr_pick<PXB_SCR_P>(const pxb_config* cfg) { return lane_shape(cfg, ScrKernel<PXB_SCR_P>{}, (scr_ptr) nullptr); }
 
 }  // namespace ev
 }  // namespace pxb
 
 #if PXB_SCR_P == 1
-#include <hipcub/hipcub.hpp>
-
-namespace pxw {
-// paxos_wire.hip: per-call scratch from the device's stream-ordered pool
-// (allocated and freed on the caller's stream; pxb_shutdown destroys the pool)
-int scratch(int dev, size_t bytes, hipStream_t st, void** p);
-}  // namespace pxw
+#include "host_util.h"
 
 namespace pxsc {
 using namespace pxb::ev;
-
-constexpr uint64_t MAX_COUNT = 1ull << 30;
+using namespace pxb::host;
 
 // the extract: byte j of row i, a grid-stride loop over count * stride bytes
 __global__ __launch_bounds__(256) void paxos_extract_kernel(EvParams p, uint32_t P, uint32_t N, uint32_t depth,
@@ -180,21 +157,19 @@ struct Kept {
 };
 typedef hipcub::TransformInputIterator<uint64_t, Kept, const uint32_t*> kept_iter;
 
-static int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
-static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the argument rules every call shares
 static int validate_cfg(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth) {
   if (!cfg || (count && !rows) || count > MAX_COUNT || depth > PXB_SCRIPT_MAX_DEPTH) return PXB_E_INVAL;
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
   return PXB_OK;
 }
+struct ScrPick {
+  const pxb_config* cfg;
+  template <int PM>
+  scr_ptr proposers() const { return scr_pick<PM>(cfg); }
+};
 static int pick(const pxb_config* cfg, scr_ptr* fn) {
-  const bool lg = cfg->n_ticks > 1;
-  const int w = wheel_for(cfg->delay_max);
-  *fn = cfg->n_proposers == 1   ? scr_pick_p1(cfg->n_acceptors, w, lg)
-        : cfg->n_proposers == 2 ? scr_pick_p2(cfg->n_acceptors, w, lg)
-                                : scr_pick_p3(cfg->n_acceptors, w, lg);
+  *fn = lane_proposers(cfg, ScrPick{cfg}, (scr_ptr) nullptr);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 static int validate_trace(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,
@@ -223,14 +198,6 @@ static size_t scan_bytes(uint64_t count, hipStream_t st) {
                                        (int64_t)(count + 1), st) != hipSuccess)
     return (size_t)-1;
   return need;
-}
-
-static int current_device(int* dev) {
-  return (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= 64) ? PXB_E_NODEV : PXB_OK;
-}
-static int device_count() {
-  int n = 0;
-  return (hipGetDeviceCount(&n) != hipSuccess) ? 0 : n;
 }
 
 }  // namespace pxsc

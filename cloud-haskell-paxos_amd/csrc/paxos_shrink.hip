@@ -23,12 +23,16 @@
 // grid: the stream is synchronised once per launch.  No block waits for
 // another; plain vector stores only.
 //
-// Built as three units by proposer count (-DPXB_SHR_P=1|2|3), as paxos_script.hip
-// is; the unit of P = 1 also holds the other kernels and the entry points.
+// Built as three units by proposer count (-DPXB_SHR_P=1|2|3) so that the slow
+// device compiles overlap; the unit of P = 1 also holds the other kernels and
+// the entry points.  What one candidate's lane does before its run is
+// ShrParams::begin (shrink_core.h), which tests/native/shrink_host.cpp runs on
+// the host; the shapes are lane_shapes.h's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "lane_shapes.h"
 #include "script_lane.h"
 #include "shrink_core.h"
 
@@ -38,28 +42,6 @@
 
 namespace pxb {
 namespace ev {
-
-struct ShrParams {
-  EvParams p;
-  const uint8_t* rows;              // the parents' rows
-  uint64_t stride;
-  const uint16_t* table;            // their rank tables
-  uint64_t tstride;                 // (halfwords)
-  const uint64_t* offsets;          // count + 1: the first candidate of each parent
-  uint64_t count;                   // parents
-  uint64_t total;                   // candidates of this launch (offsets[count])
-  uint32_t depth, flag_mask;
-  uint32_t prefix;                  // ranks <= j (else == j)
-  uint8_t* held;                    // total
-  uint16_t* csent;                  // total * 2 P N (nullable)
-  uint4* cres;                      // total (nullable)
-};
-
-typedef void (*shr_ptr)(ShrParams);
-// one per unit: the kernel of a shape (null: none)
-shr_ptr shr_pick_p1(uint32_t n, int w, bool lg);
-shr_ptr shr_pick_p2(uint32_t n, int w, bool lg);
-shr_ptr shr_pick_p3(uint32_t n, int w, bool lg);
 
 template <int PM, int N, int W, bool LG = false>
 __global__ __launch_bounds__(64) void paxos_shrink_kernel(ShrParams k) {
@@ -74,25 +56,10 @@ __global__ __launch_bounds__(64) void paxos_shrink_kernel(ShrParams k) {
   L.m = LdsMem{lds, lane};
   L.set_keys(k.p);
   TraceLane<Lane> T;
-  T.begin_count(1u, 0u);            // (an empty window: no records are counted)
-  bool run = c < k.total;
-  if (run) {
-    // the parent: the last i with offsets[i] <= c (offsets[0] = 0, offsets[count] = total > c)
-    uint64_t lo = 0u, hi = k.count;
-    while (hi - lo > 1u) {
-      const uint64_t mid = lo + ((hi - lo) >> 1);
-      if (k.offsets[mid] <= c) lo = mid;
-      else hi = mid;
-    }
-    const uint32_t j = (uint32_t)(c - k.offsets[lo]);
-    const uint32_t st = shrink_begin(L, k.p, k.depth, k.rows + lo * k.stride, k.table + lo * k.tstride, j,
-                                     k.prefix != 0u);
-    if (st != PXB_TRACE_OK) {       // a malformed row: not run
-      T.status = st;
-      run = false;
-    }
-  }
+  const bool run = k.begin(L, T, c);
   script_run(L, T, k.p, run);
+  // (the stores stay here: in a shared member, as begin is, the same text
+  // compiled to 200 more instructions for the shapes of 48 and 54 links)
   if (c < k.total) {
     uint16_t snt[NL];
     if (T.status == PXB_TRACE_OK) {
@@ -110,53 +77,33 @@ __global__ __launch_bounds__(64) void paxos_shrink_kernel(ShrParams k) {
   }
 }
 
-template <int PM, int W, bool LG = false>
-static shr_ptr pick_n(uint32_t n) {
-  switch (n) {
-    case 2: return paxos_shrink_kernel<PM, 2, W, LG>;
-    case 3: return paxos_shrink_kernel<PM, 3, W, LG>;
-    case 4: return paxos_shrink_kernel<PM, 4, W, LG>;
-    case 5: return paxos_shrink_kernel<PM, 5, W, LG>;
-    case 6: return paxos_shrink_kernel<PM, 6, W, LG>;
-    case 7: return paxos_shrink_kernel<PM, 7, W, LG>;
-    case 8: return paxos_shrink_kernel<PM, 8, W, LG>;
-    case 9: return paxos_shrink_kernel<PM, 9, W, LG>;
-  }
-  return nullptr;
-}
-
-// (log mode: the 8-step wheel only, as the script kernels)
+typedef void (*shr_ptr)(ShrParams);
+// the kernel of a config's shape among the unit's of PM proposers (null: none);
+// each unit specialises it for its own proposer count
 template <int PM>
-static shr_ptr pick_w(uint32_t n, int w, bool lg) {
-  if (lg) return w == 8 ? pick_n<PM, 8, true>(n) : nullptr;
-  return w == 8 ? pick_n<PM, 8>(n) : w == 16 ? pick_n<PM, 16>(n) : nullptr;
-}
+shr_ptr shr_pick(const pxb_config* cfg);
+template <> shr_ptr shr_pick<1>(const pxb_config* cfg);
+template <> shr_ptr shr_pick<2>(const pxb_config* cfg);
+template <> shr_ptr shr_pick<3>(const pxb_config* cfg);
 
-#if PXB_SHR_P == 1
-shr_ptr shr_pick_p1(uint32_t n, int w, bool lg) { return pick_w<1>(n, w, lg); }
-#elif PXB_SHR_P == 2
-shr_ptr shr_pick_p2(uint32_t n, int w, bool lg) { return pick_w<2>(n, w, lg); }
-#elif PXB_SHR_P == 3
-shr_ptr shr_pick_p3(uint32_t n, int w, bool lg) { return pick_w<3>(n, w, lg); }
-#else
-#error "PXB_SHR_P must be 1, 2 or 3"
-#endif
+template <int PM>
+struct ShrKernel {
+  template <int N, int W, bool LG>
+  shr_ptr shape() const { return paxos_shrink_kernel<PM, N, W, LG>; }
+};
+template <>
+shr_ptr shr_pick<PXB_SHR_P>(const pxb_config* cfg) { return lane_shape(cfg, ShrKernel<PXB_SHR_P>{}, (shr_ptr) nullptr); }
 
 }  // namespace ev
 }  // namespace pxb
 
 #if PXB_SHR_P == 1
-#include <hipcub/hipcub.hpp>
-
-namespace pxw {
-// paxos_wire.hip: per-call scratch from the device's stream-ordered pool
-int scratch(int dev, size_t bytes, hipStream_t st, void** p);
-}  // namespace pxw
+#include "host_util.h"
 
 namespace pxsh {
 using namespace pxb::ev;
+using namespace pxb::host;
 
-constexpr uint64_t MAX_COUNT = 1ull << 30;
 constexpr uint32_t ACTIVE = 0xFFFFFFFFu;          // state: still shrinking (else the final status)
 constexpr uint32_t PH_INIT = 0u, PH_SINGLES = 1u, PH_PREFIXES = 2u;
 constexpr uint32_t NO_PREFIX = 0xFFFFFFFFu;
@@ -351,20 +298,13 @@ __global__ __launch_bounds__(256) void shrink_first_counts_kernel(uint32_t* cnt,
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i <= count; i += step) cnt[i] = i < count ? 1u : 0u;
 }
 
-struct Widen {
-  __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& c) const { return c; }
+struct ShrPick {
+  const pxb_config* cfg;
+  template <int PM>
+  shr_ptr proposers() const { return shr_pick<PM>(cfg); }
 };
-typedef hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> cnt_iter;
-
-static int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
-static size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int pick(const pxb_config* cfg, shr_ptr* fn) {
-  const bool lg = cfg->n_ticks > 1;
-  const int w = wheel_for(cfg->delay_max);
-  *fn = cfg->n_proposers == 1   ? shr_pick_p1(cfg->n_acceptors, w, lg)
-        : cfg->n_proposers == 2 ? shr_pick_p2(cfg->n_acceptors, w, lg)
-                                : shr_pick_p3(cfg->n_acceptors, w, lg);
+  *fn = lane_proposers(cfg, ShrPick{cfg}, (shr_ptr) nullptr);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 // the argument rules both calls share
@@ -374,10 +314,6 @@ static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uin
   if ((flag_mask & 0xFFu) == 0u || max_launches == 0u) return PXB_E_INVAL;
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
   return pick(cfg, fn);
-}
-static int device_count() {
-  int n = 0;
-  return (hipGetDeviceCount(&n) != hipSuccess) ? 0 : n;
 }
 
 }  // namespace pxsh
@@ -397,7 +333,7 @@ int pxb_shrink_batch_device(const pxb_config* cfg, uint8_t* d_rows, uint64_t cou
     return PXB_E_INVAL;
   const hipStream_t st = (hipStream_t)stream;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (int rc = current_device(&dev)) return rc;
   if (count == 0) return PXB_OK;
 
   ShrCtl k{};
@@ -409,7 +345,7 @@ int pxb_shrink_batch_device(const pxb_config* cfg, uint8_t* d_rows, uint64_t cou
   k.tstride = shrink_tstride(k.d);
 
   size_t scan_b = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, cnt_iter(nullptr, Widen{}), (uint64_t*)nullptr,
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
                                        (int64_t)(count + 1), st) != hipSuccess)
     return PXB_E_HIP;
   // the call's scratch: work rows | tables | sent | counts | offsets | state | launches | faults | results | scan
@@ -464,7 +400,7 @@ int pxb_shrink_batch_device(const pxb_config* cfg, uint8_t* d_rows, uint64_t cou
     }
     // initial | singles | prefixes | singles | ...: ends when no parent has a candidate
     for (uint32_t phase = PH_INIT;; phase = phase == PH_SINGLES ? PH_PREFIXES : PH_SINGLES) {
-      e = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, cnt_iter(k.cnt, Widen{}), offsets, (int64_t)(count + 1), st);
+      e = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, widen_iter(k.cnt, Widen{}), offsets, (int64_t)(count + 1), st);
       if (e != hipSuccess) break;
       uint64_t total = 0;
       if ((e = hipMemcpyAsync(&total, offsets + count, sizeof(total), hipMemcpyDeviceToHost, st)) != hipSuccess) break;

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "lane_shapes.h"
 #include "paxos_ev_kernel.h"
 #include "paxos_trace_core.h"   // trace_record, trace_config_ok
 
@@ -71,37 +72,18 @@ __global__ __launch_bounds__(64) void paxos_trace_kernel(EvParams p, uint32_t gi
 
 typedef void (*trace_ptr)(EvParams, uint32_t, pxb_trace_step*, uint32_t, uint32_t*, uint4*);
 
-template <int PM, int W, bool E, bool LG = false>
-static trace_ptr pick_n(uint32_t n) {
-  switch (n) {
-    case 2: return paxos_trace_kernel<PM, 2, W, E, LG>;
-    case 3: return paxos_trace_kernel<PM, 3, W, E, LG>;
-    case 4: return paxos_trace_kernel<PM, 4, W, E, LG>;
-    case 5: return paxos_trace_kernel<PM, 5, W, E, LG>;
-    case 6: return paxos_trace_kernel<PM, 6, W, E, LG>;
-    case 7: return paxos_trace_kernel<PM, 7, W, E, LG>;
-    case 8: return paxos_trace_kernel<PM, 8, W, E, LG>;
-    case 9: return paxos_trace_kernel<PM, 9, W, E, LG>;
-  }
-  return nullptr;
-}
-
-// (log mode: the 8-step wheel only, as the batch kernels' LG shape)
+// the kernel of a config's shape (lane_shapes.h)
+template <int PM, bool E>
+struct TraceKernel {
+  template <int N, int W, bool LG>
+  trace_ptr shape() const { return paxos_trace_kernel<PM, N, W, E, LG>; }
+};
 template <bool E>
-static trace_ptr pick(uint32_t pm, uint32_t n, int w, bool lg) {
-  switch (pm * 1000 + (lg ? 500u : 0u) + (uint32_t)w) {
-    case 1008: return pick_n<1, 8, E>(n);
-    case 1016: return pick_n<1, 16, E>(n);
-    case 2008: return pick_n<2, 8, E>(n);
-    case 2016: return pick_n<2, 16, E>(n);
-    case 3008: return pick_n<3, 8, E>(n);
-    case 3016: return pick_n<3, 16, E>(n);
-    case 1508: return pick_n<1, 8, E, true>(n);
-    case 2508: return pick_n<2, 8, E, true>(n);
-    case 3508: return pick_n<3, 8, E, true>(n);
-  }
-  return nullptr;
-}
+struct TracePick {
+  const pxb_config* cfg;
+  template <int PM>
+  trace_ptr proposers() const { return lane_shape(cfg, TraceKernel<PM, E>{}, (trace_ptr) nullptr); }
+};
 
 }  // namespace ev
 }  // namespace pxb
@@ -114,12 +96,11 @@ extern "C" int pxb_trace_instance(const pxb_config* cfg, uint64_t instance, pxb_
   // ticker, 14-bit commands, Execute-driven logs); eligible() holds its delays
   // to the 8-step wheel
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
-  const bool lg = cfg->n_ticks > 1;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
   const bool prod = (cfg->flags & PXB_CFG_TRACE_PRODUCTION) != 0u;
-  const trace_ptr fn = prod ? pick<true>(cfg->n_proposers, cfg->n_acceptors, wheel_for(cfg->delay_max), lg)
-                            : pick<false>(cfg->n_proposers, cfg->n_acceptors, wheel_for(cfg->delay_max), lg);
+  const trace_ptr fn = prod ? lane_proposers(cfg, TracePick<true>{cfg}, (trace_ptr) nullptr)
+                            : lane_proposers(cfg, TracePick<false>{cfg}, (trace_ptr) nullptr);
   if (!fn) return PXB_E_INVAL;
   EvParams p = make_params(cfg);
   p.first_instance = instance;

@@ -18,12 +18,16 @@
 // The wave stays together: lanes that have finished idle, and the loop's back
 // edge is one ballot (EvLane::step's any_lane ballots then see the live lanes).
 //
-// Built as three units by proposer count (-DPXB_TRB_P=1|2|3), as paxos_ev.hip
-// is; the unit of P = 1 also holds the entry points.
+// Built as three units by proposer count (-DPXB_TRB_P=1|2|3) so that the slow
+// device compiles overlap; the unit of P = 1 also holds the entry points.  What
+// one lane does around its run is TrbParams::begin / finish (paxos_trace_core.h),
+// which tests/native/trace_host.cpp runs on the host; the shapes are
+// lane_shapes.h's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "lane_shapes.h"
 #include "paxos_ev_kernel.h"
 #include "paxos_trace_core.h"
 
@@ -34,25 +38,6 @@
 namespace pxb {
 namespace ev {
 
-struct TrbParams {
-  EvParams p;
-  const uint64_t* ids;
-  uint64_t count;
-  uint32_t smin, smax, tail;
-  uint32_t* cnt;                    // in-window records per instance (count pass: out; write pass: in)
-  const uint64_t* offsets;          // write pass: d_offsets
-  pxb_trace_step* out;              // write pass: d_records (count pass: null)
-  uint64_t capacity;
-  uint32_t* status;                 // count pass, nullable
-  uint4* res;                       // count pass, nullable
-};
-
-typedef void (*trb_ptr)(TrbParams);
-// one per unit: the kernel of a shape (null: none)
-trb_ptr trb_pick_p1(uint32_t n, int w, bool lg, bool prod);
-trb_ptr trb_pick_p2(uint32_t n, int w, bool lg, bool prod);
-trb_ptr trb_pick_p3(uint32_t n, int w, bool lg, bool prod);
-
 // the shapes and pools of paxos_trace_kernel
 template <int PM, int N, int W, bool EARLY, bool LG = false>
 __global__ __launch_bounds__(64) void paxos_trace_batch_kernel(TrbParams k) {
@@ -62,83 +47,47 @@ __global__ __launch_bounds__(64) void paxos_trace_batch_kernel(TrbParams k) {
   __shared__ uint32_t lds[S::WORDS * 64];
   const uint32_t lane = threadIdx.x;
   const uint64_t i0 = (uint64_t)blockIdx.x * 64u, i = i0 + lane;
-  const bool write = k.out != nullptr;
-  if (write && k.offsets[i0] >= k.capacity) return;     // (wave-uniform; offsets ascend: nothing of this block fits)
+  if (k.out != nullptr && k.offsets[i0] >= k.capacity) return;   // (wave-uniform; offsets ascend: nothing of this block fits)
   Lane L;
   L.m = LdsMem{lds, lane};
   L.set_keys(k.p);
   TraceLane<Lane> T;
-  T.begin_count(k.smin, k.smax);
-  bool run = i < k.count;
-  if (run && write) {
-    const uint32_t c = k.cnt[i];
-    const uint64_t base = k.offsets[i];
-    run = (c != 0u) & (base < k.capacity);
-    if (run) T.begin_write(k.smin, k.smax, c, k.tail, k.out + base, k.capacity - base);
-  }
-  if (run) {
-    EvParams pl = k.p;              // (the lane's own id: init takes first_instance + g)
-    pl.first_instance = k.ids[i];
-    L.init(pl, 0u);
-  }
+  bool run = k.begin(L, T, i);
   while (any_lane(run)) {
     if (run) run = T.iter(L, k.p);
   }
-  if (!write && i < k.count) {
-    k.cnt[i] = T.n;
-    if (k.status) k.status[i] = T.status;
-    if (k.res) k.res[i] = make_uint4(T.res[0], T.res[1], T.res[2], T.res[3]);
-  }
+  k.finish(L, T, i);
 }
 
-template <int PM, int W, bool E, bool LG = false>
-static trb_ptr pick_n(uint32_t n) {
-  switch (n) {
-    case 2: return paxos_trace_batch_kernel<PM, 2, W, E, LG>;
-    case 3: return paxos_trace_batch_kernel<PM, 3, W, E, LG>;
-    case 4: return paxos_trace_batch_kernel<PM, 4, W, E, LG>;
-    case 5: return paxos_trace_batch_kernel<PM, 5, W, E, LG>;
-    case 6: return paxos_trace_batch_kernel<PM, 6, W, E, LG>;
-    case 7: return paxos_trace_batch_kernel<PM, 7, W, E, LG>;
-    case 8: return paxos_trace_batch_kernel<PM, 8, W, E, LG>;
-    case 9: return paxos_trace_batch_kernel<PM, 9, W, E, LG>;
-  }
-  return nullptr;
-}
+typedef void (*trb_ptr)(TrbParams);
+// the kernel of a config's shape among the unit's of PM proposers (null: none);
+// each unit specialises it for its own proposer count
+template <int PM>
+trb_ptr trb_pick(const pxb_config* cfg);
+template <> trb_ptr trb_pick<1>(const pxb_config* cfg);
+template <> trb_ptr trb_pick<2>(const pxb_config* cfg);
+template <> trb_ptr trb_pick<3>(const pxb_config* cfg);
 
-// (log mode: the 8-step wheel only, as the batch kernels' LG shape)
-template <int PM, bool E>
-static trb_ptr pick_w(uint32_t n, int w, bool lg) {
-  if (lg) return w == 8 ? pick_n<PM, 8, E, true>(n) : nullptr;
-  return w == 8 ? pick_n<PM, 8, E>(n) : w == 16 ? pick_n<PM, 16, E>(n) : nullptr;
+template <int PM, bool EARLY>
+struct TrbKernel {
+  template <int N, int W, bool LG>
+  trb_ptr shape() const { return paxos_trace_batch_kernel<PM, N, W, EARLY, LG>; }
+};
+template <>
+trb_ptr trb_pick<PXB_TRB_P>(const pxb_config* cfg) {
+  return (cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? lane_shape(cfg, TrbKernel<PXB_TRB_P, true>{}, (trb_ptr) nullptr)
+                                                 : lane_shape(cfg, TrbKernel<PXB_TRB_P, false>{}, (trb_ptr) nullptr);
 }
-
-#if PXB_TRB_P == 1
-trb_ptr trb_pick_p1(uint32_t n, int w, bool lg, bool prod) { return prod ? pick_w<1, true>(n, w, lg) : pick_w<1, false>(n, w, lg); }
-#elif PXB_TRB_P == 2
-trb_ptr trb_pick_p2(uint32_t n, int w, bool lg, bool prod) { return prod ? pick_w<2, true>(n, w, lg) : pick_w<2, false>(n, w, lg); }
-#elif PXB_TRB_P == 3
-trb_ptr trb_pick_p3(uint32_t n, int w, bool lg, bool prod) { return prod ? pick_w<3, true>(n, w, lg) : pick_w<3, false>(n, w, lg); }
-#else
-#error "PXB_TRB_P must be 1, 2 or 3"
-#endif
 
 }  // namespace ev
 }  // namespace pxb
 
 #if PXB_TRB_P == 1
-#include <hipcub/hipcub.hpp>
-
-namespace pxw {
-// paxos_wire.hip: per-call scratch from the device's stream-ordered pool
-// (allocated and freed on the caller's stream; pxb_shutdown destroys the pool)
-int scratch(int dev, size_t bytes, hipStream_t st, void** p);
-}  // namespace pxw
+#include "host_util.h"
 
 namespace pxtb {
 using namespace pxb::ev;
-
-constexpr uint64_t MAX_COUNT = 1ull << 30;
+using namespace pxb::host;
 
 // the scan's input: what the selection keeps of an instance's in-window records
 struct Kept {
@@ -147,8 +96,11 @@ struct Kept {
 };
 typedef hipcub::TransformInputIterator<uint64_t, Kept, const uint32_t*> kept_iter;
 
-int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
-size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct TrbPick {
+  const pxb_config* cfg;
+  template <int PM>
+  trb_ptr proposers() const { return trb_pick<PM>(cfg); }
+};
 
 // the argument rules of both forms; *fn: the shape's kernel
 int validate(const pxb_config* cfg, const void* ids, uint64_t count, const pxb_trace_sel* sel, const void* records,
@@ -157,11 +109,7 @@ int validate(const pxb_config* cfg, const void* ids, uint64_t count, const pxb_t
   if (sel && sel->reserved != 0u) return PXB_E_INVAL;
   if (!records && capacity) return PXB_E_INVAL;
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
-  const bool prod = (cfg->flags & PXB_CFG_TRACE_PRODUCTION) != 0u, lg = cfg->n_ticks > 1;
-  const int w = wheel_for(cfg->delay_max);
-  *fn = cfg->n_proposers == 1   ? trb_pick_p1(cfg->n_acceptors, w, lg, prod)
-        : cfg->n_proposers == 2 ? trb_pick_p2(cfg->n_acceptors, w, lg, prod)
-                                : trb_pick_p3(cfg->n_acceptors, w, lg, prod);
+  *fn = lane_proposers(cfg, TrbPick{cfg}, (trb_ptr) nullptr);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 
@@ -226,7 +174,7 @@ int pxb_trace_batch_device(const pxb_config* cfg, const uint64_t* d_ids, uint64_
     return PXB_E_INVAL;
   const hipStream_t st = (hipStream_t)stream;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (int rc = current_device(&dev)) return rc;
   if (count == 0) {
     const hipError_t e = hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st);
     return (e == hipSuccess) ? PXB_OK : hip_fail(e);
@@ -249,8 +197,7 @@ int pxb_trace_batch(const pxb_config* cfg, const uint64_t* ids, uint64_t count, 
   using namespace pxtb;
   trb_ptr fn = nullptr;
   if (int rc = validate(cfg, ids, count, sel, records, capacity, offsets, &fn)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
+  if (device_count() == 0) return PXB_E_NODEV;
   if (count == 0) {
     offsets[0] = 0;
     if (n_records) *n_records = 0;

@@ -2,10 +2,13 @@
 // per-lane state machine (paxos_ev.h): the record of one step (trace_record,
 // used by pxb_trace_instance and pxb_trace_batch) and the per-lane core of the
 // batched trace (TraceLane: one instance, one iteration at a time, counting or
-// writing the records a selection keeps).  The host unit test
+// writing the records a selection keeps), and the form every lane kernel of
+// the tool families has (the lane jobs: TrbParams::begin / finish here).  The
+// host unit test
 // (tests/native/trace_host.cpp) compiles the same code over a host accessor.
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/paxos_batch.h"
 #include "paxos_ev.h"
@@ -164,6 +167,74 @@ struct TraceLane {
       return false;
     }
     return true;
+  }
+};
+
+// four result words to an output: one 16-byte store on the device (hipMalloc'ed
+// and checked by the entry points); on the host the caller's buffer, of which
+// no alignment is known
+__host__ __device__ __forceinline__ void store4(uint4* o, const uint32_t (&r)[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *o = make_uint4(r[0], r[1], r[2], r[3]);
+#else
+  memcpy(reinterpret_cast<unsigned char*>(o), r, 16);
+#endif
+}
+
+// ---- the lane jobs ----
+// Every lane kernel of the tool families (paxos_trace_batch_kernel,
+// paxos_script_kernel, paxos_shrink_kernel, paxos_explore_kernel) is one shape:
+//   L.m = its LDS words;  L.set_keys(k.p);
+//   what job g is and how its lane starts  (-> run)
+//   the wave's lanes to their ends under TraceLane
+//   every store to the job's outputs
+// with k the kernel's parameter struct.  Where it leaves the compiled kernel as
+// it was, the text before and after the loop is a plain C++ member of that
+// struct, begin(L, T, g) -> run and finish(L, T, g), which the host build of the
+// lane (tests/native/*_host.cpp) runs over host pointers with its own guarded
+// loop in between: both here, begin alone for the shrinker (shrink_core.h).
+// The script and the explore kernels spell theirs out (DESIGN.md §3 has the
+// register counts and timings that decided each).
+
+// pxb_trace_batch: job i is ids[i]
+struct TrbParams {
+  EvParams p;
+  const uint64_t* ids;
+  uint64_t count;
+  uint32_t smin, smax, tail;
+  uint32_t* cnt;                    // in-window records per instance (count pass: out; write pass: in)
+  const uint64_t* offsets;          // write pass: d_offsets
+  pxb_trace_step* out;              // write pass: d_records (count pass: null)
+  uint64_t capacity;
+  uint32_t* status;                 // count pass, nullable
+  uint4* res;                       // count pass, nullable
+
+  // the count pass or the write pass of instance i (out: which); true: the lane runs
+  template <class Lane>
+  __host__ __device__ __forceinline__ bool begin(Lane& L, TraceLane<Lane>& T, uint64_t i) const {
+    const bool write = out != nullptr;
+    T.begin_count(smin, smax);
+    bool run = i < count;
+    if (run && write) {
+      const uint32_t c = cnt[i];
+      const uint64_t base = offsets[i];
+      run = (c != 0u) & (base < capacity);
+      if (run) T.begin_write(smin, smax, c, tail, out + base, capacity - base);
+    }
+    if (run) {
+      EvParams pl = p;             // (the lane's own id: init takes first_instance + g)
+      pl.first_instance = ids[i];
+      L.init(pl, 0u);
+    }
+    return run;
+  }
+  template <class Lane>
+  __host__ __device__ __forceinline__ void finish(const Lane&, const TraceLane<Lane>& T, uint64_t i) const {
+    if (out == nullptr && i < count) {
+      cnt[i] = T.n;
+      if (status) status[i] = T.status;
+      if (res) store4(res + i, T.res);
+    }
   }
 };
 

@@ -28,8 +28,10 @@
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "host_util.h"
 
 namespace pxw {
+using namespace pxb::host;
 
 // constructor tags in declaration order (putSum of Data.Binary.Generic)
 constexpr uint32_t PROPOSE = 1;                         // ClientRequest: AskForTicket 0, Propose 1, Execute 2
@@ -345,8 +347,6 @@ __global__ __launch_bounds__(DTILE) void decode_kernel(const uint8_t* __restrict
 std::mutex g_mu;
 hipMemPool_t g_pool[64];
 
-int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
-
 unsigned tiles_of(uint64_t n, int tile) { return (unsigned)((n + tile - 1) / tile); }
 
 int scratch(int dev, size_t bytes, hipStream_t st, void** p) {
@@ -400,7 +400,7 @@ int pxb_wire_size(const pxb_msg* d_msgs, uint64_t count, uint32_t type, uint64_t
   if (hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st) != hipSuccess) return PXB_E_HIP;
   if (count == 0) return PXB_OK;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (int rc = current_device(&dev)) return rc;
   // offsets[1..count] = inclusive sum of the record sizes, computed as the
   // scan reads the messages
   hipcub::TransformInputIterator<uint64_t, SizeOp, const pxb_msg*> sizes(d_msgs, SizeOp{type});
@@ -432,13 +432,13 @@ int pxb_wire_encode_all(const pxb_msg* d_msgs, uint64_t count, uint32_t type, ui
   if (count == 0) return (hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st) == hipSuccess) ? PXB_OK : PXB_E_HIP;
   if (!d_msgs || !d_bytes) return PXB_E_INVAL;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PXB_E_NODEV;
+  if (int rc = current_device(&dev)) return rc;
   const uint64_t tiles = tiles_of(count, ETILE);
   size_t need = 0;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, (uint64_t*)nullptr, (uint64_t*)nullptr, (int64_t)tiles, st) !=
       hipSuccess)
     return PXB_E_HIP;
-  const size_t arr = ((tiles * sizeof(uint64_t)) + 255) & ~(size_t)255;
+  const size_t arr = pad256(tiles * sizeof(uint64_t));
   void* buf = nullptr;
   if (int rc = scratch(dev, 2 * arr + need, st, &buf)) return rc;
   uint64_t* tsum = reinterpret_cast<uint64_t*>(buf);

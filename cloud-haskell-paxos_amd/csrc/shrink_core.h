@@ -15,7 +15,9 @@
 //
 // Here: the entry decode, the per-entry fault test, the per-entry
 // apply / settle step, a fault's signature record and the FNV-1a-64 fold, the
-// candidate's draw source and start, and the predicate.  The walk over a
+// candidate's draw source and start, the predicate, and the candidate kernel's
+// parameters with what one lane does before its run (ShrParams::begin: the lane
+// job of paxos_trace_core.h).  The walk over a
 // parent's entries (a 64-lane wave with ballots on the device, a loop on the
 // host) is the caller's.
 #pragma once
@@ -194,6 +196,45 @@ __host__ __device__ inline bool shrink_holds(uint32_t status, uint32_t flags, co
   for (uint32_t i = 0; i < n_links; ++i) mx = sent[i] > mx ? sent[i] : mx;
   return (status == PXB_TRACE_OK) & ((flags & 0xFFu & flag_mask) != 0u) & (mx <= depth);
 }
+
+// ---- the lane job (paxos_trace_core.h) of the candidate kernel: job c is candidate c of the launch ----
+struct ShrParams {
+  EvParams p;
+  const uint8_t* rows;              // the parents' rows
+  uint64_t stride;
+  const uint16_t* table;            // their rank tables
+  uint64_t tstride;                 // (halfwords)
+  const uint64_t* offsets;          // count + 1: the first candidate of each parent
+  uint64_t count;                   // parents
+  uint64_t total;                   // candidates of this launch (offsets[count])
+  uint32_t depth, flag_mask;
+  uint32_t prefix;                  // ranks <= j (else == j)
+  uint8_t* held;                    // total
+  uint16_t* csent;                  // total * 2 P N (nullable)
+  uint4* cres;                      // total (nullable)
+
+  template <class Lane, class Trace>
+  __host__ __device__ __forceinline__ bool begin(Lane& L, Trace& T, uint64_t c) const {
+    T.begin_count(1u, 0u);          // (an empty window: no records are counted)
+    bool run = c < total;
+    if (run) {
+      // the parent: the last i with offsets[i] <= c (offsets[0] = 0, offsets[count] = total > c)
+      uint64_t lo = 0u, hi = count;
+      while (hi - lo > 1u) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (offsets[mid] <= c) lo = mid;
+        else hi = mid;
+      }
+      const uint32_t j = (uint32_t)(c - offsets[lo]);
+      const uint32_t st = shrink_begin(L, p, depth, rows + lo * stride, table + lo * tstride, j, prefix != 0u);
+      if (st != PXB_TRACE_OK) {     // a malformed row: not run
+        T.status = st;
+        run = false;
+      }
+    }
+    return run;
+  }
+};
 
 }  // namespace ev
 }  // namespace pxb

@@ -14,48 +14,17 @@
 #include <vector>
 
 #include "../../cloud-haskell-paxos_amd/csrc/explore_core.h"
+#include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
 #include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
+#include "host_lane.h"
 
 using namespace pxb;
 using namespace pxb::ev;
 
 namespace {
 
-#define PXB_HCHK(c)                                                                                         \
-  do {                                                                                                     \
-    if (!(c)) {                                                                                            \
-      fprintf(stderr, "explore_host: LDS access out of the shape's words: %s (%s:%d)\n", #c, __FILE__, __LINE__); \
-      abort();                                                                                             \
-    }                                                                                                      \
-  } while (0)
-// one lane's words, every access checked against the shape's S::WORDS (as shrink_host.cpp's)
-struct HostMem {
-  uint32_t* w;
-  uint32_t n;
-  uint32_t ld(uint32_t i) const { PXB_HCHK(i < n); return w[i]; }
-  void st(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] = v; }
-  uint32_t ld16(uint32_t base, uint32_t i) const {
-    PXB_HCHK(2u * base + i < 2u * n);
-    return reinterpret_cast<const uint16_t*>(w + base)[i];
-  }
-  void st16(uint32_t base, uint32_t i, uint32_t v) const {
-    PXB_HCHK(2u * base + i < 2u * n);
-    reinterpret_cast<uint16_t*>(w + base)[i] = (uint16_t)v;
-  }
-  uint32_t ld16h(uint32_t i, uint32_t half) const {
-    PXB_HCHK(i < n && half < 2u);
-    return reinterpret_cast<const uint16_t*>(w + i)[half];
-  }
-  void st16h(uint32_t i, uint32_t half, uint32_t v) const {
-    PXB_HCHK(i < n && half < 2u);
-    reinterpret_cast<uint16_t*>(w + i)[half] = (uint16_t)v;
-  }
-  uint32_t ldh(uint32_t base, uint32_t i) const { return ld16(base, i); }
-  void sth(uint32_t base, uint32_t i, uint32_t v) const { st16(base, i, v); }
-  void orw(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] |= v; }
-};
-
-// one candidate: what one lane of paxos_explore_kernel does
+// one candidate: what one lane of paxos_explore_kernel does (spelled out here
+// as in the kernel: paxos_explore.hip says why it is not shared)
 struct Cand {
   const pxb_config* cfg;
   const ExploreSpace* e;
@@ -66,19 +35,15 @@ struct Cand {
 
 template <int PM, int N, int W, bool LG>
 int run_shape(const Cand& a) {
-  using SL = ScriptLane<PM, N, W, LG, HostMem, ExploreDraws>;
-  using S = typename SL::S;
-  using Lane = typename SL::Lane;
+  using Lane = typename ScriptLane<PM, N, W, LG, HostMem, ExploreDraws>::Lane;
   constexpr uint32_t NL = 2u * PM * N;
   *a.flags = 0u;
   const ExploreByte x = explore_byte(*a.e, explore_unrank(*a.e, a.c), a.row, N, a.site_depth, a.depth);
   if (explore_parent_bad(a.row, PM) || explore_changes_keep(x)) return 0;
-  std::vector<uint32_t> buf(S::WORDS, 0xDEADBEEFu);      // garbage: init must set what it reads
   EvParams p = make_params(a.cfg);
   p.first_instance = 0;
-  Lane L;
-  L.m = HostMem{buf.data(), (uint32_t)S::WORDS};
-  L.set_keys(p);
+  HostLane<Lane> H(p);
+  Lane& L = H.L;
   TraceLane<Lane> T;
   const uint64_t guard_max = 100000ull * a.cfg->step_cap;   // a hang is a test failure
   uint64_t guard = 0;
@@ -101,34 +66,19 @@ int dispatch(const Cand& a) {
   return run_shape<1, 3, 8, false>(a);
 }
 #else
-template <int PM, int W, bool LG>
-int run_n(const Cand& a) {
-  switch (a.cfg->n_acceptors) {
-    case 2: return run_shape<PM, 2, W, LG>(a);
-    case 3: return run_shape<PM, 3, W, LG>(a);
-    case 4: return run_shape<PM, 4, W, LG>(a);
-    case 5: return run_shape<PM, 5, W, LG>(a);
-    case 6: return run_shape<PM, 6, W, LG>(a);
-    case 7: return run_shape<PM, 7, W, LG>(a);
-    case 8: return run_shape<PM, 8, W, LG>(a);
-    case 9: return run_shape<PM, 9, W, LG>(a);
-  }
-  return -1;
-}
+// (the shapes of lane_shapes.h; -1: none)
 template <int PM>
-int run_w(const Cand& a) {
-  const int w = wheel_for(a.cfg->delay_max);
-  if (a.cfg->n_ticks > 1) return w == 8 ? run_n<PM, 8, true>(a) : -1;
-  return w == 8 ? run_n<PM, 8, false>(a) : run_n<PM, 16, false>(a);
-}
-int dispatch(const Cand& a) {
-  switch (a.cfg->n_proposers) {
-    case 1: return run_w<1>(a);
-    case 2: return run_w<2>(a);
-    case 3: return run_w<3>(a);
-  }
-  return -1;
-}
+struct RunShape {
+  const Cand& a;
+  template <int N, int W, bool LG>
+  int shape() const { return run_shape<PM, N, W, LG>(a); }
+};
+struct RunProposers {
+  const Cand& a;
+  template <int PM>
+  int proposers() const { return lane_shape(a.cfg, RunShape<PM>{a}, -1); }
+};
+int dispatch(const Cand& a) { return lane_proposers(a.cfg, RunProposers{a}, -1); }
 #endif
 
 }  // namespace

@@ -14,87 +14,38 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
 #include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
 #include "../../cloud-haskell-paxos_amd/csrc/shrink_core.h"
+#include "host_lane.h"
 
 using namespace pxb;
 using namespace pxb::ev;
 
 namespace {
 
-#define PXB_HCHK(c)                                                                                        \
-  do {                                                                                                    \
-    if (!(c)) {                                                                                           \
-      fprintf(stderr, "shrink_host: LDS access out of the shape's words: %s (%s:%d)\n", #c, __FILE__, __LINE__); \
-      abort();                                                                                            \
-    }                                                                                                     \
-  } while (0)
-// one lane's words, every access checked against the shape's S::WORDS (as script_host.cpp's)
-struct HostMem {
-  uint32_t* w;
-  uint32_t n;
-  uint32_t ld(uint32_t i) const { PXB_HCHK(i < n); return w[i]; }
-  void st(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] = v; }
-  uint32_t ld16(uint32_t base, uint32_t i) const {
-    PXB_HCHK(2u * base + i < 2u * n);
-    return reinterpret_cast<const uint16_t*>(w + base)[i];
-  }
-  void st16(uint32_t base, uint32_t i, uint32_t v) const {
-    PXB_HCHK(2u * base + i < 2u * n);
-    reinterpret_cast<uint16_t*>(w + base)[i] = (uint16_t)v;
-  }
-  uint32_t ld16h(uint32_t i, uint32_t half) const {
-    PXB_HCHK(i < n && half < 2u);
-    return reinterpret_cast<const uint16_t*>(w + i)[half];
-  }
-  void st16h(uint32_t i, uint32_t half, uint32_t v) const {
-    PXB_HCHK(i < n && half < 2u);
-    reinterpret_cast<uint16_t*>(w + i)[half] = (uint16_t)v;
-  }
-  uint32_t ldh(uint32_t base, uint32_t i) const { return ld16(base, i); }
-  void sth(uint32_t base, uint32_t i, uint32_t v) const { st16(base, i, v); }
-  void orw(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] |= v; }
-};
-
-// one candidate: what one lane of paxos_shrink_kernel does
+// candidate `c` of a launch as paxos_shrink_kernel runs it
 struct Cand {
   const pxb_config* cfg;
-  const uint8_t* row;
-  const uint16_t* table;
-  uint32_t depth, j;
-  bool prefix;
-  uint32_t flag_mask;
-  bool* held;
-  uint16_t* sent;                   // 2 P N
-  uint32_t* res;                    // 4
+  const ShrParams* k;
+  uint64_t c;
 };
 
+// ShrParams::begin is the kernel's own; the stores after the run are spelled out
+// here as in the kernel (paxos_shrink.hip says why they are not shared)
 template <int PM, int N, int W, bool LG>
 int run_shape(const Cand& a) {
-  using SL = ScriptLane<PM, N, W, LG, HostMem, ShrinkDraws>;
-  using S = typename SL::S;
-  using Lane = typename SL::Lane;
-  std::vector<uint32_t> buf(S::WORDS, 0xDEADBEEFu);      // garbage: init must set what it reads
-  EvParams p = make_params(a.cfg);
-  p.first_instance = 0;
-  Lane L;
-  L.m = HostMem{buf.data(), (uint32_t)S::WORDS};
-  L.set_keys(p);
+  using Lane = typename ScriptLane<PM, N, W, LG, HostMem, ShrinkDraws>::Lane;
+  constexpr uint32_t NL = 2u * PM * N;
+  const ShrParams& k = *a.k;
+  HostLane<Lane> H(k.p);
   TraceLane<Lane> T;
-  const uint64_t guard_max = 100000ull * a.cfg->step_cap;   // a hang is a test failure
-  uint64_t guard = 0;
-  T.begin_count(1u, 0u);
-  const uint32_t st = shrink_begin(L, p, a.depth, a.row, a.table, a.j, a.prefix);
-  if (st != PXB_TRACE_OK) {
-    T.status = st;
-  } else {
-    while (T.iter(L, p))
-      if (++guard > guard_max) return -100;
-  }
-  if (T.status == PXB_TRACE_OK) script_sent(L, a.sent);
-  else memset(a.sent, 0, 2u * PM * N * sizeof(uint16_t));
-  *a.held = shrink_holds(T.status, T.res[3], a.sent, 2u * PM * N, a.depth, a.flag_mask);
-  memcpy(a.res, T.res, 16);
+  if (!host_run(k, H.L, T, a.c, a.cfg->step_cap)) return -100;
+  uint16_t* const snt = k.csent + a.c * NL;
+  if (T.status == PXB_TRACE_OK) script_sent(H.L, snt);
+  else memset(snt, 0, NL * sizeof(uint16_t));
+  k.held[a.c] = shrink_holds(T.status, T.res[3], snt, NL, k.depth, k.flag_mask) ? 1u : 0u;
+  memcpy(reinterpret_cast<unsigned char*>(k.cres) + 16u * a.c, T.res, 16);
   return 0;
 }
 
@@ -106,35 +57,62 @@ int dispatch(const Cand& a) {
   return run_shape<2, 5, 8, false>(a);
 }
 #else
-template <int PM, int W, bool LG>
-int run_n(const Cand& a) {
-  switch (a.cfg->n_acceptors) {
-    case 2: return run_shape<PM, 2, W, LG>(a);
-    case 3: return run_shape<PM, 3, W, LG>(a);
-    case 4: return run_shape<PM, 4, W, LG>(a);
-    case 5: return run_shape<PM, 5, W, LG>(a);
-    case 6: return run_shape<PM, 6, W, LG>(a);
-    case 7: return run_shape<PM, 7, W, LG>(a);
-    case 8: return run_shape<PM, 8, W, LG>(a);
-    case 9: return run_shape<PM, 9, W, LG>(a);
-  }
-  return -1;
-}
+// (the shapes of lane_shapes.h; -1: none)
 template <int PM>
-int run_w(const Cand& a) {
-  const int w = wheel_for(a.cfg->delay_max);
-  if (a.cfg->n_ticks > 1) return w == 8 ? run_n<PM, 8, true>(a) : -1;
-  return w == 8 ? run_n<PM, 8, false>(a) : run_n<PM, 16, false>(a);
-}
-int dispatch(const Cand& a) {
-  switch (a.cfg->n_proposers) {
-    case 1: return run_w<1>(a);
-    case 2: return run_w<2>(a);
-    case 3: return run_w<3>(a);
-  }
-  return -1;
-}
+struct RunShape {
+  const Cand& a;
+  template <int N, int W, bool LG>
+  int shape() const { return run_shape<PM, N, W, LG>(a); }
+};
+struct RunProposers {
+  const Cand& a;
+  template <int PM>
+  int proposers() const { return lane_shape(a.cfg, RunShape<PM>{a}, -1); }
+};
+int dispatch(const Cand& a) { return lane_proposers(a.cfg, RunProposers{a}, -1); }
 #endif
+
+// One launch of the candidate kernel over one parent: its candidates 0 .. n - 1.
+// The launch has three parents, the row between two that have no candidate
+// (offsets 0, 0, n, n), so that ShrParams::begin's search over the offsets runs.
+struct Launch {
+  std::vector<uint8_t> held;        // n
+  std::vector<uint16_t> sent;       // n * 2 P N
+  std::vector<uint32_t> res;        // n * 4
+  int run(const pxb_config* cfg, const uint8_t* row, const uint16_t* table, uint32_t depth, uint32_t flag_mask,
+          uint32_t n, bool prefix) {
+    const ShrinkDims d{cfg->n_proposers, cfg->n_acceptors, depth, cfg->delay_max};
+    const uint32_t NL = 2u * d.P * d.N;
+    const uint64_t stride = script_stride(d.P, d.N, depth), tstride = shrink_tstride(d);
+    const uint64_t offsets[4] = {0u, 0u, n, n};
+    std::vector<uint8_t> rows((size_t)(3u * stride), 0u);
+    std::vector<uint16_t> tables((size_t)(3u * tstride), (uint16_t)SHR_NONE);
+    memcpy(rows.data() + stride, row, (size_t)stride);
+    memcpy(tables.data() + tstride, table, (size_t)tstride * sizeof(uint16_t));
+    held.assign(n, 0u);
+    sent.assign((size_t)n * NL, 0u);
+    res.assign((size_t)n * 4u, 0u);
+    ShrParams k{};
+    k.p = make_params(cfg);
+    k.p.first_instance = 0;
+    k.rows = rows.data();
+    k.stride = stride;
+    k.table = tables.data();
+    k.tstride = tstride;
+    k.offsets = offsets;
+    k.count = 3u;
+    k.total = n;
+    k.depth = depth;
+    k.flag_mask = flag_mask;
+    k.prefix = prefix;
+    k.held = held.data();
+    k.csent = sent.data();
+    k.cres = reinterpret_cast<uint4*>(res.data());
+    for (uint64_t c = 0; c < n; ++c)
+      if (int rc = dispatch(Cand{cfg, &k, c})) return rc;
+    return 0;
+  }
+};
 
 constexpr uint32_t NO_PREFIX = 0xFFFFFFFFu;
 
@@ -159,10 +137,12 @@ int shrink_one(const pxb_config* cfg, uint8_t* row, uint32_t depth, uint32_t fla
   const uint32_t E = shrink_entries(d), NL = 2u * d.P * d.N;
   std::vector<uint16_t> tab((size_t)shrink_tstride(d), (uint16_t)SHR_NONE), psent(NL, 0), cs(NL, 0);
   uint32_t res[4] = {0u, 0u, 0u, 0u}, launches = 1u, nf = 0u, st;
-  bool held = false;
-  if (int rc = dispatch(Cand{cfg, row, tab.data(), depth, 0u, false, flag_mask, &held, cs.data(), res})) return rc;
+  Launch l;
+  if (int rc = l.run(cfg, row, tab.data(), depth, flag_mask, 1u, false)) return rc;
+  memcpy(res, l.res.data(), 16);
+  cs = l.sent;
   do {
-    if (!held) {
+    if (!l.held[0]) {
       st = PXB_SHRINK_NOT_INPUT;
       break;
     }
@@ -184,40 +164,31 @@ int shrink_one(const pxb_config* cfg, uint8_t* row, uint32_t depth, uint32_t fla
         break;
       }
       // singles
-      std::vector<uint8_t> h(nf);
-      uint32_t r4[4];
-      for (uint32_t j = 0; j < nf; ++j) {
-        if (int rc = dispatch(Cand{cfg, row, tab.data(), depth, j, false, flag_mask, &held, cs.data(), r4})) return rc;
-        h[j] = held;
-      }
+      if (int rc = l.run(cfg, row, tab.data(), depth, flag_mask, nf, false)) return rc;
       ++launches;
       uint32_t nrem = 0u;
       for (uint32_t t = 0; t < E; ++t) {
         const uint32_t r = tab[t];
-        tab[t] = (uint16_t)((r != SHR_NONE && h[r]) ? nrem++ : SHR_NONE);
+        tab[t] = (uint16_t)((r != SHR_NONE && l.held[r]) ? nrem++ : SHR_NONE);
       }
       if (nrem == 0u) {
         st = PXB_SHRINK_MINIMAL;
         break;
       }
       // prefixes: the longest that holds
-      uint32_t best = NO_PREFIX;
-      std::vector<uint16_t> bs(NL, 0);
-      for (uint32_t j = 0; j < nrem; ++j) {
-        if (int rc = dispatch(Cand{cfg, row, tab.data(), depth, j, true, flag_mask, &held, cs.data(), r4})) return rc;
-        if (held) {
-          best = j;
-          bs = cs;
-          memcpy(res, r4, 16);
-        }
-      }
+      if (int rc = l.run(cfg, row, tab.data(), depth, flag_mask, nrem, true)) return rc;
       ++launches;
+      uint32_t best = NO_PREFIX;
+      for (uint32_t j = 0; j < nrem; ++j)
+        if (l.held[j]) best = j;
       if (best == NO_PREFIX) {
         st = PXB_SHRINK_UNSTABLE;
         break;
       }
-      nf = accept_and_enumerate(d, row, tab.data(), bs.data(), best);
-      psent = bs;
+      cs.assign(l.sent.begin() + (size_t)best * NL, l.sent.begin() + (size_t)(best + 1u) * NL);
+      memcpy(res, l.res.data() + (size_t)best * 4u, 16);
+      nf = accept_and_enumerate(d, row, tab.data(), cs.data(), best);
+      psent = cs;
     }
   } while (0);
   const bool shrunk = st == PXB_SHRINK_MINIMAL || st == PXB_SHRINK_BUDGET || st == PXB_SHRINK_UNSTABLE;

@@ -13,47 +13,15 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
 #include "../../cloud-haskell-paxos_amd/csrc/paxos_ev_kernel.h"
 #include "../../cloud-haskell-paxos_amd/csrc/paxos_trace_core.h"
+#include "host_lane.h"
 
 using namespace pxb;
 using namespace pxb::ev;
 
 namespace {
-
-#define PXB_HCHK(c)                                                                                        \
-  do {                                                                                                   \
-    if (!(c)) {                                                                                          \
-      fprintf(stderr, "trace_host: LDS access out of the shape's words: %s (%s:%d)\n", #c, __FILE__, __LINE__); \
-      abort();                                                                                           \
-    }                                                                                                    \
-  } while (0)
-// one lane's words, every access checked against the shape's S::WORDS (as ev_host.cpp's checked accessor)
-struct HostMem {
-  uint32_t* w;
-  uint32_t n;
-  uint32_t ld(uint32_t i) const { PXB_HCHK(i < n); return w[i]; }
-  void st(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] = v; }
-  uint32_t ld16(uint32_t base, uint32_t i) const {
-    PXB_HCHK(2u * base + i < 2u * n);
-    return reinterpret_cast<const uint16_t*>(w + base)[i];
-  }
-  void st16(uint32_t base, uint32_t i, uint32_t v) const {
-    PXB_HCHK(2u * base + i < 2u * n);
-    reinterpret_cast<uint16_t*>(w + base)[i] = (uint16_t)v;
-  }
-  uint32_t ld16h(uint32_t i, uint32_t half) const {
-    PXB_HCHK(i < n && half < 2u);
-    return reinterpret_cast<const uint16_t*>(w + i)[half];
-  }
-  void st16h(uint32_t i, uint32_t half, uint32_t v) const {
-    PXB_HCHK(i < n && half < 2u);
-    reinterpret_cast<uint16_t*>(w + i)[half] = (uint16_t)v;
-  }
-  uint32_t ldh(uint32_t base, uint32_t i) const { return ld16(base, i); }
-  void sth(uint32_t base, uint32_t i, uint32_t v) const { st16(base, i, v); }
-  void orw(uint32_t i, uint32_t v) const { PXB_HCHK(i < n); w[i] |= v; }
-};
 
 struct Args {
   const pxb_config* cfg;
@@ -67,40 +35,37 @@ struct Args {
   pxb_result* result;
 };
 
-// what one lane of paxos_trace_batch_kernel does for its instance: the count
-// pass, then (records kept and room for some) the write pass from offset 0
+// Instance `a.id` as paxos_trace_batch_kernel runs it (TrbParams over one id):
+// the count pass, then (records kept and room for some) the write pass from
+// offset 0
 template <int PM, int N, int W, bool EARLY, bool LG>
 int run_shape(const Args& a) {
   constexpr int POOL = EvPool<PM, N, false, LG>::value;
-  using S = Shape<PM, N, POOL, W, false, LG>;
   using Lane = EvLane<PM, N, POOL, W, false, HostMem, EARLY, LG>;
-  std::vector<uint32_t> buf(S::WORDS, 0xDEADBEEFu);      // garbage: init must set what it reads
-  EvParams p = make_params(a.cfg);
-  p.first_instance = 0;
-  EvParams pl = p;
-  pl.first_instance = a.id;
-  Lane L;
-  L.m = HostMem{buf.data(), (uint32_t)S::WORDS};
-  L.set_keys(p);
+  const uint64_t offset0 = 0u;
+  TrbParams k{};
+  k.p = make_params(a.cfg);
+  k.p.first_instance = 0;
+  k.ids = &a.id;
+  k.count = 1u;
+  k.smin = a.smin, k.smax = a.smax, k.tail = a.tail;
+  k.cnt = a.n_window;
+  k.offsets = &offset0;
+  k.capacity = a.capacity;
+  k.status = a.status;
+  k.res = reinterpret_cast<uint4*>(a.result);
+  HostLane<Lane> H(k.p);
   TraceLane<Lane> T;
-  const uint64_t guard_max = 100000ull * a.cfg->step_cap;   // a hang is a test failure
-  uint64_t guard = 0;
-  T.begin_count(a.smin, a.smax);
-  L.init(pl, 0u);
-  while (T.iter(L, p))
-    if (++guard > guard_max) return -100;
-  const uint32_t cnt = T.n, kept = trace_kept(cnt, a.tail);
-  *a.n_window = cnt;
+  if (!host_run(k, H.L, T, 0u, a.cfg->step_cap)) return -100;
+  k.finish(H.L, T, 0u);
+  // (the scan's part: what the selection keeps of the instance's count)
+  const uint32_t kept = trace_kept(*a.n_window, a.tail);
   *a.n_kept = kept;
-  *a.status = T.status;
-  memcpy(a.result, T.res, 16);
   if (kept == 0u || a.capacity == 0u || !a.records) return 0;
-  std::fill(buf.begin(), buf.end(), 0xDEADBEEFu);
-  T.begin_write(a.smin, a.smax, cnt, a.tail, a.records, a.capacity);
-  L.init(pl, 0u);
-  guard = 0;
-  while (T.iter(L, p))
-    if (++guard > guard_max) return -100;
+  std::fill(H.buf.begin(), H.buf.end(), 0xDEADBEEFu);
+  k.out = a.records;
+  if (!host_run(k, H.L, T, 0u, a.cfg->step_cap)) return -100;
+  k.finish(H.L, T, 0u);
   return 0;
 }
 
@@ -112,37 +77,22 @@ int dispatch(const Args& a) {
   return (c->flags & PXB_CFG_TRACE_PRODUCTION) ? run_shape<2, 5, 8, true, false>(a) : run_shape<2, 5, 8, false, false>(a);
 }
 #else
-template <int PM, int W, bool E, bool LG>
-int run_n(const Args& a) {
-  switch (a.cfg->n_acceptors) {
-    case 2: return run_shape<PM, 2, W, E, LG>(a);
-    case 3: return run_shape<PM, 3, W, E, LG>(a);
-    case 4: return run_shape<PM, 4, W, E, LG>(a);
-    case 5: return run_shape<PM, 5, W, E, LG>(a);
-    case 6: return run_shape<PM, 6, W, E, LG>(a);
-    case 7: return run_shape<PM, 7, W, E, LG>(a);
-    case 8: return run_shape<PM, 8, W, E, LG>(a);
-    case 9: return run_shape<PM, 9, W, E, LG>(a);
-  }
-  return -1;
-}
+// (the shapes of lane_shapes.h; -1: none)
 template <int PM, bool E>
-int run_w(const Args& a) {
-  const int w = wheel_for(a.cfg->delay_max);
-  if (a.cfg->n_ticks > 1) return w == 8 ? run_n<PM, 8, E, true>(a) : -1;
-  return w == 8 ? run_n<PM, 8, E, false>(a) : run_n<PM, 16, E, false>(a);
-}
+struct RunShape {
+  const Args& a;
+  template <int N, int W, bool LG>
+  int shape() const { return run_shape<PM, N, W, E, LG>(a); }
+};
 template <bool E>
-int run_p(const Args& a) {
-  switch (a.cfg->n_proposers) {
-    case 1: return run_w<1, E>(a);
-    case 2: return run_w<2, E>(a);
-    case 3: return run_w<3, E>(a);
-  }
-  return -1;
-}
+struct RunProposers {
+  const Args& a;
+  template <int PM>
+  int proposers() const { return lane_shape(a.cfg, RunShape<PM, E>{a}, -1); }
+};
 int dispatch(const Args& a) {
-  return (a.cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? run_p<true>(a) : run_p<false>(a);
+  return (a.cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? lane_proposers(a.cfg, RunProposers<true>{a}, -1)
+                                                   : lane_proposers(a.cfg, RunProposers<false>{a}, -1);
 }
 #endif
 

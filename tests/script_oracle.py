@@ -26,9 +26,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "script_host.cpp")
 OUT = os.path.join(HERE, "native", "_build", "libscript_host.so")
-DEPS = [SRC] + [os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
-                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h",
-                          "script_core.h")] + [os.path.join(ROOT, "include", "paxos_batch.h")]
+DEPS = [SRC, os.path.join(HERE, "native", "host_lane.h")] + [
+    os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
+    for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h",
+              "lane_shapes.h", "script_core.h", "script_lane.h")] + [os.path.join(ROOT, "include", "paxos_batch.h")]
 HIPCC = "/opt/rocm/bin/hipcc"
 U32 = 0xFFFFFFFF
 _real_params, _real_philox = R.instance_params, R.philox4x32_10

@@ -8,6 +8,7 @@ import pytest
 
 import explore_oracle as X
 import pxb
+import script_oracle as SO
 
 pytestmark = pytest.mark.gpu
 GPU = pxb._run_scripted_runner
@@ -223,3 +224,33 @@ def test_minimal_candidates_through_shrink_batch(gpu_lib):
     # and the README's line: the first of them traced
     rec, offs, st, _ = pxb.trace_scripted(cfg, rows[:1], depth)
     assert st[0] == pxb.TRACE_OK and len(rec) == offs[1] > 0
+
+
+# ---- 8. every kernel unit ---------------------------------------------------------------------------------------
+# (P, N, delay_max): every proposer-count unit with the smallest and the largest
+# acceptor count on the 8-step wheel, and one shape on the 16-step wheel
+UNIT_SHAPES = [pytest.param(p, n, 4, id="%d-%d" % (p, n)) for p in (1, 2, 3) for n in (2, 9)] + [
+    pytest.param(2, 3, 12, id="2-3-wheel16")]
+
+
+def unit_case(P, N, delay_max):
+    """(cfg, parents, depth, site_depth, radius): the benign row and an extracted
+    row of a faulty config, every site changed once (T <= 1 + 54 * 4)."""
+    cfg = pxb.Config(seed=0x5EED0100 + 16 * P + N, n_proposers=P, n_acceptors=N, loss_ppm=100000,
+                     delay_max=delay_max, skew_max=3, crash_ppm=100000, crash_len_max=8, crash_start_max=8,
+                     step_cap=256)
+    depth = 8
+    return cfg, np.stack([X.benign_row(cfg, depth), SO.host_extract(cfg, [1], depth)[0]]), depth, 1, 1
+
+
+@pytest.mark.parametrize("P,N,delay_max", UNIT_SHAPES)
+def test_every_kernel_unit(gpu_lib, P, N, delay_max):
+    """The list in both modes, the counts and the status equal the host build's
+    (tests/native/explore_host.cpp) exactly."""
+    cfg, parents, depth, sd, R = unit_case(P, N, delay_max)
+    for minimal in (False, True):
+        h = X.host_explore(cfg, parents, depth, sd, R, 0xFE, minimal=minimal)
+        ids, n, counts, status = pxb.explore(cfg, parents, depth, sd, R, 0xFE, minimal=minimal)
+        assert n == h["n"] and np.array_equal(ids, h["ids"])
+        assert np.array_equal(counts, h["counts"]) and np.array_equal(status, h["status"])
+    assert (status == pxb.TRACE_OK).all()

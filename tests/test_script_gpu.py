@@ -236,13 +236,20 @@ def test_g7_sweep_then_shrink(gpu_lib):
     assert done == 3, "%d of %d matches shrunk; passed over (not shrink inputs): %s" % (done, len(ids), passed_over)
 
 
-@pytest.mark.parametrize("P,N", [(p, n) for p in (1, 2, 3) for n in (2, 9)])
-def test_g8_every_kernel_unit_launches(gpu_lib, P, N):
+# (P, N, delay_max): every proposer-count unit with the smallest and the largest
+# acceptor count on the 8-step wheel, and one shape on the 16-step wheel
+UNIT_SHAPES = [pytest.param(p, n, 4, id="%d-%d" % (p, n)) for p in (1, 2, 3) for n in (2, 9)] + [
+    pytest.param(2, 3, 12, id="2-3-wheel16")]
+
+
+@pytest.mark.parametrize("P,N,delay_max", UNIT_SHAPES)
+def test_g8_every_kernel_unit_launches(gpu_lib, P, N, delay_max):
     """64 rows of P proposers and N acceptors with random overrides: the GPU
     equals the host build (every proposer-count unit, the smallest and the
-    largest acceptor count)."""
-    cfg = pxb.Config(seed=0x5EED0100 + 16 * P + N, n_proposers=P, n_acceptors=N, loss_ppm=100000, delay_max=4,
-                     skew_max=3, crash_ppm=100000, crash_len_max=8, crash_start_max=8, step_cap=256)
+    largest acceptor count; both wheels)."""
+    cfg = pxb.Config(seed=0x5EED0100 + 16 * P + N, n_proposers=P, n_acceptors=N, loss_ppm=100000,
+                     delay_max=delay_max, skew_max=3, crash_ppm=100000, crash_len_max=8, crash_start_max=8,
+                     step_cap=256)
     depth = 12
     rows = SO.random_overrides(cfg, list(range(64)), depth, seed=P * 10 + N)
     h = SO.host_run(cfg, rows, depth, capacity=cfg.step_cap + 1)

@@ -82,13 +82,19 @@ def test_minimal_and_replays(gpu_lib):
     assert (status2 == status).all() and (res2 == res).all() and (sent2 == sent).all()
 
 
-@pytest.mark.parametrize("P", [1, 2, 3])
-@pytest.mark.parametrize("N", [2, 9])
-def test_every_kernel_unit(gpu_lib, P, N):
-    """Every proposer-count unit, the smallest and the largest acceptor count."""
-    cfg = pxb.Config(seed=0x5EED0100 + 16 * P + N, n_proposers=P, n_acceptors=N, loss_ppm=100000, delay_max=4,
-                     skew_max=3, crash_ppm=100000, crash_len_max=8, crash_start_max=8, step_cap=256)
-    _, _, rr = compare(cfg, np.arange(64, dtype=np.uint64), 0x3F, depth=32)
+# (P, N, delay_max, depth): every proposer-count unit with the smallest and the
+# largest acceptor count on the 8-step wheel, and one shape on the 16-step wheel
+UNIT_SHAPES = [pytest.param(p, n, 4, 32, id="%d-%d" % (n, p)) for n in (2, 9) for p in (1, 2, 3)] + [
+    pytest.param(2, 3, 12, 12, id="3-2-wheel16")]
+
+
+@pytest.mark.parametrize("P,N,delay_max,depth", UNIT_SHAPES)
+def test_every_kernel_unit(gpu_lib, P, N, delay_max, depth):
+    """Every proposer-count unit, the smallest and the largest acceptor count; both wheels."""
+    cfg = pxb.Config(seed=0x5EED0100 + 16 * P + N, n_proposers=P, n_acceptors=N, loss_ppm=100000,
+                     delay_max=delay_max, skew_max=3, crash_ppm=100000, crash_len_max=8, crash_start_max=8,
+                     step_cap=256)
+    _, _, rr = compare(cfg, np.arange(64, dtype=np.uint64), 0x3F, depth=depth)
     assert sum(r["status"] != pxb.SHRINK_NOT_INPUT for r in rr) >= 1
 
 

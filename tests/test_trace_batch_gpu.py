@@ -2,6 +2,7 @@
 id, exactly what pxb_trace_instance gives one call at a time, in the order of
 the id list, with the window / tail selection and the capacity rule applied."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
@@ -35,14 +36,15 @@ def runs(rec, offs):
 
 
 @pytest.mark.parametrize("production", [False, True])
-@pytest.mark.parametrize("c", [3, 4, 5, 7])
+@pytest.mark.parametrize("c", [3, 4, 5, 7, "3-wheel16"])
 def test_equals_the_single_trace(gpu_lib, c, production):
     """ids 0..129 (two full waves and a two-lane third; config 5: 0..255, which
-    hold instances beyond the link capacities): every instance's records and
-    result are pxb_trace_instance's, byte for byte, and it is BAILED exactly
-    where pxb_trace_instance refuses."""
-    cfg = pxb.CONFIGS[c]
-    ids = np.arange(256 if c == 5 else 130, dtype=np.uint64)
+    hold instances beyond the link capacities; config 3 with delays up to 12,
+    the 16-step wheel: 0..63): every instance's records and result are
+    pxb_trace_instance's, byte for byte, and it is BAILED exactly where
+    pxb_trace_instance refuses."""
+    cfg = dataclasses.replace(pxb.CONFIGS[3], delay_max=12) if c == "3-wheel16" else pxb.CONFIGS[c]
+    ids = np.arange({5: 256, "3-wheel16": 64}.get(c, 130), dtype=np.uint64)
     rec, offs, status, res = pxb.trace_batch(cfg, ids, production=production)
     assert offs[0] == 0 and offs[-1] == len(rec) and (np.diff(offs.astype(np.int64)) >= 0).all()
     got = runs(rec, offs)

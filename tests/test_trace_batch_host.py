@@ -25,9 +25,10 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "trace_host.cpp")
 OUT = os.path.join(HERE, "native", "_build", "libtrace_host.so")
 EXE = os.path.join(HERE, "native", "_build", "trace_host_san")
-DEPS = [SRC] + [os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
-                for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h")] + \
-       [os.path.join(ROOT, "include", "paxos_batch.h")]
+DEPS = [SRC, os.path.join(HERE, "native", "host_lane.h")] + [
+    os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
+    for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h",
+              "lane_shapes.h")] + [os.path.join(ROOT, "include", "paxos_batch.h")]
 HIPCC = "/opt/rocm/bin/hipcc"
 U32 = 0xFFFFFFFF
 SELECTIONS = [(0, U32, 0), (10, 40, 0), (0, U32, 1), (5, 5, 0), (7, 3, 0), (20, 200, 3)]
