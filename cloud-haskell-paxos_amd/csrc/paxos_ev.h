@@ -312,6 +312,15 @@ struct EvOut {
 struct PhiloxDraws {
   static constexpr bool kPhilox = true;
 };
+// A source with a static kTap = true (events_core.h: EventDraws) is also told
+// what each acceptor op and each proposer op handled and produced:
+//   tap_acc(acc, a, p, kind, x, z, fate, snd, pw, rz),
+//   tap_prop(pin, q, r, rkind, px, py, pz, k0, x0, x1, c2n, spd)
+// behind an `if constexpr`, so that a source without it compiles as before.
+template <class T, class = void>
+struct draws_tap : std::false_type {};
+template <class T>
+struct draws_tap<T, std::void_t<decltype(T::kTap)>> : std::integral_constant<bool, T::kTap> {};
 
 // EARLY: a step may end with the copies of its last broadcast still to send
 // (see end_op); the trace kernel turns it off so that its per-step records
@@ -496,14 +505,23 @@ struct EvLane : Src {
   }
 
   // fields of the packed proposer state of p (finish, trace)
-  __host__ __device__ uint32_t p_ticket(int p) const { return pw0[p] & 0xFFFu; }
-  __host__ __device__ uint32_t p_mr_t(int p) const { return (pw0[p] >> 12) & 0xFFFu; }
-  __host__ __device__ uint32_t p_acks(int p) const { return (pw0[p] >> 24) & 15u; }
-  __host__ __device__ uint32_t p_state(int p) const { return (pw0[p] >> 28) & 3u; }
-  __host__ __device__ uint32_t p_pending(int p) const { return (pw0[p] >> 30) & 1u; }
-  __host__ __device__ uint32_t p_mr_v(int p) const { return pw1[p] & 3u; }
-  __host__ __device__ uint32_t p_r2_v(int p) const { return (pw1[p] >> 2) & 3u; }
-  __host__ __device__ uint32_t p_cmd(int p) const { return (pw1[p] >> 4) & 3u; }
+  // (w_*: of the words themselves, for a caller that selected them by a per-lane index, get(pw0, q))
+  __host__ __device__ static uint32_t w_ticket(uint32_t w0) { return w0 & 0xFFFu; }
+  __host__ __device__ static uint32_t w_mr_t(uint32_t w0) { return (w0 >> 12) & 0xFFFu; }
+  __host__ __device__ static uint32_t w_acks(uint32_t w0) { return (w0 >> 24) & 15u; }
+  __host__ __device__ static uint32_t w_state(uint32_t w0) { return (w0 >> 28) & 3u; }
+  __host__ __device__ static uint32_t w_pending(uint32_t w0) { return (w0 >> 30) & 1u; }
+  __host__ __device__ static uint32_t w_mr_v(uint32_t w1) { return w1 & 3u; }
+  __host__ __device__ static uint32_t w_r2_v(uint32_t w1) { return (w1 >> 2) & 3u; }
+  __host__ __device__ static uint32_t w_cmd(uint32_t w1) { return (w1 >> 4) & 3u; }
+  __host__ __device__ uint32_t p_ticket(int p) const { return w_ticket(pw0[p]); }
+  __host__ __device__ uint32_t p_mr_t(int p) const { return w_mr_t(pw0[p]); }
+  __host__ __device__ uint32_t p_acks(int p) const { return w_acks(pw0[p]); }
+  __host__ __device__ uint32_t p_state(int p) const { return w_state(pw0[p]); }
+  __host__ __device__ uint32_t p_pending(int p) const { return w_pending(pw0[p]); }
+  __host__ __device__ uint32_t p_mr_v(int p) const { return w_mr_v(pw1[p]); }
+  __host__ __device__ uint32_t p_r2_v(int p) const { return w_r2_v(pw1[p]); }
+  __host__ __device__ uint32_t p_cmd(int p) const { return w_cmd(pw1[p]); }
 
   // broadcast ring slot `slot` of proposer q: halfword `half` of word `word`
   // (two proposers: one word per slot, the proposer picks the half)
@@ -1151,6 +1169,7 @@ struct EvLane : Src {
       pw = grant ? p_gr : pw;
     }
     const bool snd1 = live & !is_exec;              // the reply, on link a -> p
+    if constexpr (draws_tap<Src>::value) Src::tap_acc(acc, a, p, kind, x, z, dead ? 1u : isol ? 2u : 0u, snd1, pw, rz);
     m.st(S::REQ + L, acc ? rq2 + ((S::CMP && snd1) ? 1u << S::KSH : 0u) : wq);
 
     // ================= the reply, on a -> p (SEMANTICS §5) =================
@@ -1267,6 +1286,7 @@ struct EvLane : Src {
         put(pw1, q, w1n);
         if constexpr (LG) put(pw2, q, t_go ? Tn : (s_maj & (PDb == 0u)) ? 0u : CT);   // handleTick: c<id>.<Tn>
         const uint32_t k0o = ask ? ASK : o_maj ? PROPOSE : s_maj ? EXECUTE : NONE;
+        if constexpr (draws_tap<Src>::value) Src::tap_prop(pin, q, r, rkind, px, py, pz, k0o, ask ? Tn : T, Tn, C2n, sPD);
         broadcast(q, k0o, ask ? Tn : T, C2n, k0o != NONE, Tn, sPD, C2n);
       }
     }
@@ -1359,27 +1379,31 @@ struct EvLane : Src {
     return n;
   }
 
-  // final per-acceptor outputs (digest, record) of an ended instance
-  __host__ __device__ uint32_t log_len_of(int a) const { return (LG ? accv[LG ? a : 0] : accw[a]) >> A_LEN; }
+  // final per-acceptor outputs (digest, record) of an ended instance; the w_
+  // forms take the acceptor's words (A = accw, V = accv in log mode, else A, D =
+  // accd), for a caller that selected them by a per-lane index, get(accw, a)
+  __host__ __device__ static uint32_t w_log_len(uint32_t V) { return V >> A_LEN; }
+  __host__ __device__ uint32_t log_len_of(int a) const { return w_log_len(LG ? accv[LG ? a : 0] : accw[a]); }
   // (single decree: log lengths < 32 fit the first byte, so FNV-1a over the
   // bytes (len, 0, 0, 0) is (h ^ len) * prime^4)
-  __host__ __device__ uint32_t digest_of(int a) const {
+  __host__ __device__ static uint32_t w_digest(uint32_t D, uint32_t len) {
     if constexpr (LG) {
-      return fnv_u32(accd[a], log_len_of(a));
+      return fnv_u32(D, len);
     } else {
       constexpr uint32_t P = 0x01000193u, P2 = P * P, P4 = P2 * P2;
       static_assert(A_LEN_MAX < 256, "one-byte log length");
-      return (accd[a] ^ log_len_of(a)) * P4;
+      return (D ^ len) * P4;
     }
   }
-  __host__ __device__ void record_of(int a, uint32_t r[4]) const {
-    const uint32_t A = accw[a];
-    const uint32_t val = LG ? accv[LG ? a : 0] & 0x3FFFu : (A >> 24) & 3u;
+  __host__ __device__ uint32_t digest_of(int a) const { return w_digest(accd[a], log_len_of(a)); }
+  __host__ __device__ static void w_record(uint32_t A, uint32_t V, uint32_t r[4]) {
+    const uint32_t val = LG ? V & 0x3FFFu : (A >> 24) & 3u;
     r[0] = A & 0xFFFu;
     r[1] = (A >> 12) & 0xFFFu;
     r[2] = val ? code_of(val) : 0u;
-    r[3] = log_len_of(a) | (((A >> A_DEAD) & 1u) << 31);
+    r[3] = w_log_len(V) | (((A >> A_DEAD) & 1u) << 31);
   }
+  __host__ __device__ void record_of(int a, uint32_t r[4]) const { w_record(accw[a], LG ? accv[LG ? a : 0] : accw[a], r); }
 };
 
 // Launch parameters from the ABI config (host side; mirrors pxb_run_device).

@@ -16,10 +16,34 @@
 namespace pxb {
 namespace ev {
 
+// proposer p's packed words (pw0, pw1, pw2: paxos_ev.h) as the record's pxb_trace_prop;
+// from the words, so that a caller may select them by a per-lane index
+template <class Lane>
+__host__ __device__ __forceinline__ void trace_prop(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t p,
+                                                    pxb_trace_prop& q) {
+  q.ticket = (int32_t)Lane::w_ticket(w0);
+  q.acks = Lane::w_acks(w0);
+  q.state = Lane::w_state(w0);
+  q.mr_t = (int32_t)Lane::w_mr_t(w0);
+  q.pending = Lane::w_pending(w0);
+  if constexpr (Lane::S::LG) {
+    // log mode: 14-bit commands id [13:12] | t [11:0] (mr_v | r2_v << 14 in
+    // pw1), the proposer's own command c<p+1>.<t> with t in pw2 (0: Nothing)
+    const uint32_t mv = w1 & 0x3FFFu, rv = (w1 >> 14) & 0x3FFFu, ct = w2;
+    q.cmd = ct ? ((p + 1u) << 24) | ct : 0u;
+    q.mr_v = mv ? Lane::code_of(mv) : 0u;
+    q.r2_v = rv ? Lane::code_of(rv) : 0u;
+  } else {
+    const uint32_t code = 1u;   // every command is c<id>.1 (docs/SEMANTICS.md §2)
+    q.cmd = Lane::w_cmd(w1) ? ((Lane::w_cmd(w1) << 24) | code) : 0u;
+    q.mr_v = Lane::w_mr_v(w1) ? ((Lane::w_mr_v(w1) << 24) | code) : 0u;
+    q.r2_v = Lane::w_r2_v(w1) ? ((Lane::w_r2_v(w1) << 24) | code) : 0u;
+  }
+}
+
 template <class Lane>
 __host__ __device__ void trace_record(const Lane& L, uint32_t step, pxb_trace_step* r) {
   constexpr int PM = Lane::S::PM, N = Lane::S::N;
-  constexpr bool LG = Lane::S::LG;
   constexpr bool EARLY = Lane::kEarly;
   r->step = step;
   // (production variant: copies of a broadcast still to send are not on the
@@ -38,26 +62,7 @@ __host__ __device__ void trace_record(const Lane& L, uint32_t step, pxb_trace_st
   }
   for (int p = 0; p < PXB_MAX_PROPOSERS; ++p) {
     pxb_trace_prop q = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (p < PM && (uint32_t)p < L.P) {
-      q.ticket = (int32_t)L.p_ticket(p);
-      q.acks = L.p_acks(p);
-      q.state = L.p_state(p);
-      q.mr_t = (int32_t)L.p_mr_t(p);
-      q.pending = L.p_pending(p);
-      if constexpr (LG) {
-        // log mode: 14-bit commands id [13:12] | t [11:0] (mr_v | r2_v << 14 in
-        // pw1), the proposer's own command c<p+1>.<t> with t in pw2 (0: Nothing)
-        const uint32_t mv = L.pw1[p] & 0x3FFFu, rv = (L.pw1[p] >> 14) & 0x3FFFu, ct = L.pw2[p];
-        q.cmd = ct ? (((uint32_t)p + 1u) << 24) | ct : 0u;
-        q.mr_v = mv ? Lane::code_of(mv) : 0u;
-        q.r2_v = rv ? Lane::code_of(rv) : 0u;
-      } else {
-        const uint32_t code = 1u;   // every command is c<id>.1 (docs/SEMANTICS.md §2)
-        q.cmd = L.p_cmd(p) ? ((L.p_cmd(p) << 24) | code) : 0u;
-        q.mr_v = L.p_mr_v(p) ? ((L.p_mr_v(p) << 24) | code) : 0u;
-        q.r2_v = L.p_r2_v(p) ? ((L.p_r2_v(p) << 24) | code) : 0u;
-      }
-    }
+    if (p < PM && (uint32_t)p < L.P) trace_prop<Lane>(L.pw0[p], L.pw1[p], L.pw2[p], (uint32_t)p, q);
     r->prop[p] = q;
   }
 }

@@ -21,8 +21,9 @@ struct ScriptLane {
 };
 
 // every lane of the wave to its end (host: the one lane); `run`: this lane started
-template <class Lane>
-__host__ __device__ __forceinline__ void script_run(Lane& L, TraceLane<Lane>& T, const EvParams& kp, bool run) {
+// (T: what turns an iteration into output, TraceLane<Lane> or events_core.h's EventLane<Lane>)
+template <class Lane, class Wrap>
+__host__ __device__ __forceinline__ void script_run(Lane& L, Wrap& T, const EvParams& kp, bool run) {
   while (any_lane(run)) {
     if (run) run = T.iter(L, kp);
   }

@@ -46,6 +46,11 @@ module PaxosBatch
   , scheduleExtract
   , runScripted
   , traceScripted
+  , Actor (..)
+  , Fate (..)
+  , Message (..)
+  , TraceEvent (..)
+  , traceEvents
   , ShrinkStatus (..)
   , Shrunk (..)
   , shrinkBatch
@@ -185,6 +190,10 @@ foreign import ccall safe "pxb_run_scripted"
 foreign import ccall safe "pxb_trace_scripted"
   c_pxb_trace_scripted :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Word64
                        -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
+
+foreign import ccall safe "pxb_trace_events"
+  c_pxb_trace_events :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Word64
+                     -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
 
 foreign import ccall safe "pxb_shrink_batch"
   c_pxb_shrink_batch :: Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Word32
@@ -496,6 +505,111 @@ traceScripted cfg rows n depth sel = do
                                   traceStep <$> peekArray nw (advancePtr pb (nw * k))
                                 [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
                                 pure (Just (recs, decode v t r f)))
+
+-- | Who handled a message: acceptor @a@ or proposer @p@ (PXB_EVT_ACCEPTOR / _PROPOSER).
+data Actor = Acceptor !Int | Proposer !Int
+  deriving (Show, Eq)
+
+-- | What became of a delivered message (PXB_EVT_HANDLED / _DISCARDED_*): a dead
+-- or an isolated acceptor discards its requests; dead is told first.
+data Fate = Handled | DiscardedDead | DiscardedIsolated
+  deriving (Show, Eq, Enum)
+
+-- | One message in or out of a handler (pxb_msg): a request (ClientRequest,
+-- Common.hs:41-45), a response (ServerResponse, Common.hs:49-53) or the Tick.
+data Message
+  = AskForTicket Ticket | Propose Ticket Command | Execute Ticket
+  | Round1OK Ticket (Maybe Proposal) | HaveTicket Ticket | Round2Success
+  | Tick
+  deriving (Show)
+
+-- | One handler invocation (pxb_trace_event): the line the reference's `say`
+-- prints after a handled message (Server.hs:85, Client.hs:108) together with
+-- the messages the handler sent (the commented-out Server.hs:86, Client.hs:109).
+-- 'teFrom' is the sender's index (Nothing: the ticker); 'teAfter' the actor's
+-- state after the handler.
+data TraceEvent = TraceEvent
+  { teStep  :: !Int
+  , teActor :: !Actor
+  , teFrom  :: Maybe Int
+  , teFate  :: !Fate
+  , teIn    :: Message
+  , teOut   :: [Message]
+  , teAfter :: Either AcceptorState ProposerState
+  } deriving (Show)
+
+-- | One pxb_trace_event (24 words) as a 'TraceEvent'.
+traceEvent :: [Word32] -> TraceEvent
+traceEvent w =
+      let at k = w !! k
+          hdr = at 1
+          isAcc = hdr .&. 0xFF == 0
+          idx = fromIntegral ((hdr `shiftR` 8) .&. 0xFF) :: Int
+          peer = fromIntegral ((hdr `shiftR` 16) .&. 0xFF) :: Int
+          tk t = Ticket (fromIntegral (fromIntegral t :: Int32))
+          cmd c = if c == 0 then Nothing else Just (commandOf c)
+          prop t c = if c == 0 then Nothing else Just (tk t, commandOf c)
+          request b = case at b of
+            0 -> AskForTicket (tk (at (b + 1)))
+            1 -> Propose (tk (at (b + 1))) (commandOf (at (b + 3)))
+            _ -> Execute (tk (at (b + 1)))
+          response b = case at b of
+            0 -> Round1OK (tk (at (b + 1))) (prop (at (b + 2)) (at (b + 3)))
+            1 -> HaveTicket (tk (at (b + 1)))
+            _ -> Round2Success
+          nOut = fromIntegral (at 2) :: Int
+          outs = [if isAcc then response b else request b | k <- [0 .. nOut - 1], let b = 8 + 4 * k]
+          meta = at 19
+          after = if isAcc
+            then Left (AcceptorState (tk (at 16)) (prop (at 17) (at 18)) (fromIntegral (meta .&. 0x7FFFFFFF))
+                                     (testBit meta 31) (at 20))
+            else Right (ProposerState (tk (at 16)) (cmd (at 17)) (fromIntegral (at 18)) (fromIntegral (at 19))
+                                      (prop (at 20) (at 21)) (cmd (at 22)) (at 23 /= 0))
+      in TraceEvent (fromIntegral (at 0)) (if isAcc then Acceptor idx else Proposer idx)
+                    (if peer == 0xFF then Nothing else Just peer) (toEnum (fromIntegral (hdr `shiftR` 24)))
+                    (if isAcc then request 4 else if at 4 == 3 then Tick else response 4) outs after
+
+-- | pxb_trace_events: 'traceScripted' at the grain of single messages: for every
+-- row Nothing when its status is not OK, else its handler events in the
+-- reference model's order (docs/SEMANTICS.md §13) and its outcome.  The
+-- selection's tail must be 0.  Sizes the event buffer with a count-only call
+-- first.
+-- (additive to ABI 5: a library without the symbol fails to link)
+traceEvents :: BatchConfig -> ScriptRows -> Int -> Word32 -> TraceSel
+            -> IO (Either String [Maybe ([TraceEvent], Outcome)])
+traceEvents cfg rows n depth sel = do
+  let nw = 24                                      -- sizeof(pxb_trace_event) / 4
+      selw = [fst (selSteps sel), snd (selSteps sel), selTail sel, 0]
+      failed rc = Left <$> (c_pxb_strerror rc >>= peekCString)
+  with cfg $ \pc ->
+    withArray rows $ \prows ->
+      withArray selw $ \psel ->
+        allocaArray (n + 1) $ \poff ->
+          allocaArray (max 1 n) $ \pst ->
+            allocaArray (max 1 (4 * n)) $ \pres ->
+              allocaArray 1 $ \ptotal -> do
+                rc0 <- c_pxb_trace_events pc prows (fromIntegral n) depth psel nullPtr 0 poff pst pres ptotal
+                if rc0 /= 0
+                  then failed rc0
+                  else do
+                    [total] <- peekArray 1 ptotal
+                    buf <- mallocForeignPtrArray (max 1 (nw * fromIntegral total))
+                    withForeignPtr buf $ \pb -> do
+                      rc <- if total == 0 then pure 0
+                            else c_pxb_trace_events pc prows (fromIntegral n) depth psel pb total poff pst pres ptotal
+                      if rc /= 0
+                        then failed rc
+                        else do
+                          offs <- peekArray (n + 1) poff
+                          sts <- peekArray n pst
+                          Right <$> forM (zip3 [0 ..] (zip offs (drop 1 offs)) sts) (\(i, (o0, o1), st) ->
+                            if st /= 0
+                              then pure Nothing
+                              else do
+                                evs <- forM [fromIntegral o0 .. fromIntegral o1 - 1] $ \k ->
+                                  traceEvent <$> peekArray nw (advancePtr pb (nw * k))
+                                [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                                pure (Just (evs, decode v t r f)))
 
 -- | What 'shrinkBatch' says of one instance (PXB_SHRINK_*).
 data ShrinkStatus = ShrinkMinimal | ShrinkBudget | ShrinkNotInput | ShrinkTooMany | ShrinkUnstable

@@ -261,6 +261,10 @@ def load(path: str = LIB_PATH):
                         [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
                        ("pxb_trace_scripted",
                         [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_trace_events_device",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_trace_events",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
                        ("pxb_shrink_batch_device",
                         [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
                        ("pxb_shrink_batch",
@@ -820,6 +824,230 @@ def trace_scripted_device(cfg: Config, d_rows, count: int, depth: int, d_offsets
     check(load().pxb_trace_scripted_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sel),
                                            _ptr(d_records) if capacity else None, capacity, _ptr(d_offsets),
                                            _ptr(d_status), _ptr(d_results), s))
+
+
+# ---- handler events of scripted rows (docs/SEMANTICS.md §13) ---------------------
+EVT_ACCEPTOR, EVT_PROPOSER = 0, 1
+EVT_HANDLED, EVT_DISCARDED_DEAD, EVT_DISCARDED_ISOL = 0, 1, 2
+EVT_PEER_TICK = 0xFF
+EVENT_BYTES = 96
+
+
+class pxb_trace_prop(C.Structure):
+    _fields_ = [("ticket", C.c_int32), ("cmd", C.c_uint32), ("acks", C.c_uint32), ("state", C.c_uint32),
+                ("mr_t", C.c_int32), ("mr_v", C.c_uint32), ("r2_v", C.c_uint32), ("pending", C.c_uint32)]
+
+
+class _pxb_event_acc(C.Structure):
+    _fields_ = [("rec", pxb_acceptor_rec), ("log_digest", C.c_uint32)]
+
+
+class _pxb_event_after(C.Union):
+    _fields_ = [("acc", _pxb_event_acc), ("prop", pxb_trace_prop)]
+
+
+class pxb_trace_event(C.Structure):
+    _fields_ = [("step", C.c_uint32), ("actor", C.c_uint8), ("index", C.c_uint8), ("peer", C.c_uint8),
+                ("fate", C.c_uint8), ("n_out", C.c_uint32), ("reserved", C.c_uint32), ("in_", pxb_msg),
+                ("out", pxb_msg * 2), ("after", _pxb_event_after)]
+
+
+assert C.sizeof(pxb_trace_event) == EVENT_BYTES and C.sizeof(pxb_trace_prop) == 32
+_event_dtype = None
+
+
+def event_dtype():
+    """The numpy structured dtype of pxb_trace_event (96 bytes): step, actor,
+    index, peer, fate, n_out, reserved, in and out[2] as (kind, x, y, z), and
+    after as its 8 words (event_after_acc / event_after_prop name them)."""
+    global _event_dtype
+    if _event_dtype is None:
+        import numpy as np
+        msg = np.dtype([("kind", "<u4"), ("x", "<i4"), ("y", "<i4"), ("z", "<u4")])
+        _event_dtype = np.dtype([("step", "<u4"), ("actor", "u1"), ("index", "u1"), ("peer", "u1"), ("fate", "u1"),
+                                 ("n_out", "<u4"), ("reserved", "<u4"), ("in", msg), ("out", msg, (2,)),
+                                 ("after", "<u4", (8,))])
+        assert _event_dtype.itemsize == EVENT_BYTES
+    return _event_dtype
+
+
+def event_after_acc(ev):
+    """after.acc of an acceptor event: (t_max, t_store, val, meta, log_digest)."""
+    return tuple(int(x) for x in ev["after"][:5])
+
+
+def event_after_prop(ev):
+    """after.prop of a proposer event, in pxb_trace_prop's order: (ticket, cmd,
+    acks, state, mr_t, mr_v, r2_v, pending)."""
+    return tuple(int(x) for x in ev["after"])
+
+
+def trace_events(cfg: Config, rows, depth: int, step_min: int = 0, step_max: int = U32_MAX, capacity=None):
+    """pxb_trace_events: one record per handler invocation of every script row,
+    in the reference model's order.  Returns (events, offsets, status, results):
+    a structured array of event_dtype() holding min(total, capacity) events
+    (capacity None: all, after a sizing call), offsets uint64 (n + 1,) with
+    row i's events at [offsets[i], offsets[i + 1]), status uint32 (n,) TRACE_OK /
+    TRACE_BAILED / SCRIPT_BAD (not OK: no events, a zeroed result), results
+    uint32 (n, 4)."""
+    import numpy as np
+    lib = load()
+    rows = _script_rows(cfg, rows, depth)
+    n = len(rows)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint32)
+    res = np.zeros((n, 4), dtype=np.uint32)
+    c = cfg.to_c(0, 1)
+    sel = pxb_trace_sel(step_min, step_max, 0, 0)
+    total = C.c_uint64(0)
+    head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sel))
+    args = (_ptr(offs), _ptr(status) if n else None, _ptr(res) if n else None, C.byref(total))
+    if capacity is None:
+        check(lib.pxb_trace_events(*head, None, 0, *args))
+        capacity = total.value
+        if capacity == 0:
+            return np.zeros(0, dtype=event_dtype()), offs, status, res
+    ev = np.zeros(capacity, dtype=event_dtype())
+    check(lib.pxb_trace_events(*head, _ptr(ev) if capacity else None, capacity, *args))
+    return ev[:min(total.value, capacity)], offs, status, res
+
+
+def trace_events_ids(cfg: Config, ids, **kw):
+    """trace_events of the plain instances `ids`: all-keep rows at depth 0."""
+    return trace_events(cfg, scripts_empty(cfg, ids, 0), 0, **kw)
+
+
+def trace_events_device(cfg: Config, d_rows, count: int, depth: int, d_offsets, d_events=None, capacity: int = 0,
+                        d_status=None, d_results=None, step_min: int = 0, step_max: int = U32_MAX, stream=None):
+    """pxb_trace_events_device on torch tensors, asynchronous on `stream`: d_rows
+    uint8, d_offsets int64 (count + 1,), d_events uint8 (96 * capacity, 16-byte
+    aligned; None with capacity 0 is the sizing call), d_status int32 (count,),
+    d_results int32 (count, 4)."""
+    if d_offsets is None:
+        raise ValueError("d_offsets is required")
+    if capacity and d_events is None:
+        raise ValueError("d_events is required when capacity > 0")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_offsets", d_offsets, count + 1, 8)
+    if d_events is not None:
+        _check_bytes("d_events", d_events, EVENT_BYTES * capacity)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    c = cfg.to_c(0, 1)
+    sel = pxb_trace_sel(step_min, step_max, 0, 0)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_trace_events_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sel),
+                                         _ptr(d_events) if capacity else None, capacity, _ptr(d_offsets),
+                                         _ptr(d_status), _ptr(d_results), s))
+
+
+_REQ_NAMES = ("AskForTicket", "Propose", "Execute")
+_RSP_NAMES = ("Round1OK", "HaveTicket", "Round2Success")
+_STATE_NAMES = ("Idle", "Round1", "Round2")
+
+
+def _cmd(code):
+    return command_str(int(code)) or "-"
+
+
+def request_str(m) -> str:
+    k, x, z = int(m["kind"]), int(m["x"]), int(m["z"])
+    return "Propose(%d,%s)" % (x, _cmd(z)) if k == 1 else "%s(%d)" % (_REQ_NAMES[k], x)
+
+
+def response_str(m) -> str:
+    k, x, y, z = int(m["kind"]), int(m["x"]), int(m["y"]), int(m["z"])
+    if k == 0:
+        return "Round1OK(%d,%s)" % (x, "(%d,%s)" % (y, _cmd(z)) if z else "-")
+    return "HaveTicket(%d)" % x if k == 1 else "Round2Success"
+
+
+def event_lines(events):
+    """One readable line per event, e.g.
+    `s=3 acc1 <- p0 Propose(1,c1.1) -> Round2Success | t_max=1 store=(1,c1.1) log=0`."""
+    out = []
+    for e in events:
+        s, i, peer, n_out = int(e["step"]), int(e["index"]), int(e["peer"]), int(e["n_out"])
+        if e["actor"] == EVT_ACCEPTOR:
+            t_max, t_store, val, meta, _ = event_after_acc(e)
+            fate = int(e["fate"])
+            made = (response_str(e["out"][0]) if n_out else "-") if fate == EVT_HANDLED else \
+                "discarded (dead)" if fate == EVT_DISCARDED_DEAD else "discarded (isolated)"
+            out.append("s=%d acc%d <- p%d %s -> %s | t_max=%d store=%s log=%d%s" % (
+                s, i, peer, request_str(e["in"]), made, t_max, "(%d,%s)" % (t_store, _cmd(val)) if val else "-",
+                meta & 0x7FFFFFFF, " DEAD" if meta >> 31 else ""))
+        else:
+            ticket, cmd, acks, state, mr_t, mr_v, r2_v, pending = event_after_prop(e)
+            src = "Tick" if peer == EVT_PEER_TICK else "a%d %s" % (peer, response_str(e["in"]))
+            made = ", ".join(request_str(e["out"][j]) for j in range(n_out)) or "-"
+            out.append("s=%d prop%d <- %s -> %s | %s ticket=%d acks=%d cmd=%s%s" % (
+                s, i, src, made, _STATE_NAMES[state], ticket, acks, _cmd(cmd), " pending" if pending else ""))
+    return out
+
+
+CHART_LOST, CHART_HANDLED, CHART_DISCARDED, CHART_IN_FLIGHT = 0, 1, 2, 3
+_chart_dtype = None
+
+
+def message_chart(cfg: Config, row, depth: int, events):
+    """The per-message view of one row's events (all of them: no step window).
+    Every event's out[] is expanded into sends: a proposer broadcast is N sends,
+    to a = 0 .. N - 1, an acceptor reply is one.  The sends of a link are
+    numbered in order (the seq), and each send's loss is read from the row's link
+    byte; a keep byte (or a seq past `depth`) is a ValueError: extract the
+    schedule first.  The j-th non-lost send of a link is the j-th delivery event
+    on that link (discards count as deliveries).  Returns a structured array,
+    one record per message in send order: dirn (0: p -> a, 1: a -> p), p, a, seq,
+    kind, x, y, z, sent_step, fate (CHART_LOST / _HANDLED / _DISCARDED /
+    _IN_FLIGHT: not delivered when the run ended), delivered_step (-1: none)."""
+    global _chart_dtype
+    import numpy as np
+    if _chart_dtype is None:
+        _chart_dtype = np.dtype([("dirn", "u1"), ("p", "u1"), ("a", "u1"), ("seq", "<u4"), ("kind", "<u4"),
+                                 ("x", "<i4"), ("y", "<i4"), ("z", "<u4"), ("sent_step", "<u4"), ("fate", "u1"),
+                                 ("delivered_step", "<i4")])
+    row = _script_rows(cfg, row, depth)
+    if len(row) != 1:
+        raise ValueError("row: one script row")
+    N = cfg.n_acceptors
+    lk = script_links(cfg, row, depth)[0]
+    sends = []                                        # (dirn, p, a, msg, step)
+    deliveries = {}                                   # link -> [(step, handled, msg)]
+    for e in events:
+        i, peer, s = int(e["index"]), int(e["peer"]), int(e["step"])
+        if e["actor"] == EVT_ACCEPTOR:
+            deliveries.setdefault((0, peer, i), []).append((s, e["fate"] == EVT_HANDLED, e["in"]))
+            if e["n_out"]:
+                sends.append((1, peer, i, e["out"][0], s))
+        else:
+            if peer != EVT_PEER_TICK:
+                deliveries.setdefault((1, i, peer), []).append((s, True, e["in"]))
+            for j in range(int(e["n_out"])):
+                sends.extend((0, i, a, e["out"][j], s) for a in range(N))
+    chart = np.zeros(len(sends), dtype=_chart_dtype)
+    seqs, arrived = {}, {}
+    for r, (dirn, p, a, m, s) in zip(chart, sends):
+        link = (dirn, p, a)
+        k = seqs.get(link, 0)
+        seqs[link] = k + 1
+        b = int(lk[dirn, p, a, k]) if k < depth else SCRIPT_KEEP8
+        if b == SCRIPT_KEEP8:
+            raise ValueError("link (%d, %d, %d) seq %d is a keep entry: extract the schedule first" % (dirn, p, a, k))
+        r["dirn"], r["p"], r["a"], r["seq"], r["sent_step"] = dirn, p, a, k, s
+        r["kind"], r["x"], r["y"], r["z"] = m["kind"], m["x"], m["y"], m["z"]
+        r["delivered_step"] = -1
+        if b == 0:
+            r["fate"] = CHART_LOST
+            continue
+        j = arrived.get(link, 0)
+        arrived[link] = j + 1
+        got = deliveries.get(link, [])
+        if j < len(got):
+            r["fate"] = CHART_HANDLED if got[j][1] else CHART_DISCARDED
+            r["delivered_step"] = got[j][0]
+        else:
+            r["fate"] = CHART_IN_FLIGHT
+    return chart
 
 
 # ---- the shrinker -------------------------------------------------------------

@@ -588,6 +588,72 @@ int pxb_trace_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t coun
                        const pxb_trace_sel* sel, pxb_trace_step* records, uint64_t capacity, uint64_t* offsets,
                        uint32_t* status, pxb_result* results, uint64_t* n_records);
 
+/* ---- handler events of scripted rows (additive to ABI 5, found by symbol) -------
+ * pxb_trace_events: one record per handler invocation of a script row, at the
+ * granularity of the reference's `say` lines (Server.hs:85, Client.hs:108: the
+ * state after every handled message; the commented-out Server.hs:86 and
+ * Client.hs:109: the messages the handler sends), for many rows at once
+ * (docs/SEMANTICS.md §13).  pxb_trace_scripted tells the state at the end of
+ * each step; this tells which message was handled, by whom, and what it
+ * produced.  An all-keep row at depth 0 with base = id is the plain instance id.
+ * Messages are pxb_msg as pxb_acceptor_handle / pxb_proposer_handle take them:
+ * requests kind 0/1/2 with x = ticket, z = command (Propose only); responses
+ * kind 0/1/2 with x, (y, z) = Round1OK's stored proposal; a Tick is kind 3.
+ * Commands are (clientId << 24) | t, in single-decree and in log mode.
+ * An acceptor's out[0] is its reply.  A proposer's out[] are its broadcasts in
+ * order, the handler's own and then the restart's AskForTicket (Client.hs:185),
+ * each listed once, not once per copy.  after.acc / after.prop are what
+ * pxb_trace_step.acc[a], .log_digest[a] / .prop[p] would hold at that moment.
+ * A request that reaches a dead or an isolated acceptor is discarded: n_out = 0,
+ * the state unchanged; dead is told before isolated.
+ * A row's events come in the order of the reference model's pops: by step; in a
+ * step the acceptor phase (a ascending, then p ascending, then the link's FIFO
+ * order), then the proposer phase (p ascending: its Tick, then a ascending, then
+ * FIFO order).  sel->step_min..step_max select by event.step; sel->tail and
+ * sel->reserved must be 0.  Offsets (count + 1 entries, events), capacity,
+ * the sizing call (d_events NULL with capacity 0), d_status and d_results
+ * (both nullable), alignment (events 16 bytes), scratch and the call rules are
+ * pxb_trace_scripted's: events at or past `capacity` are counted and never
+ * written, and nothing at or past `capacity` entries is touched; a row that is
+ * not PXB_TRACE_OK has no events and a zeroed result.  The default variant only
+ * (PXB_CFG_TRACE_PRODUCTION: PXB_E_INVAL).  The write pass stages the first
+ * min(total, capacity + 256) events and a dense kernel, one thread per staged
+ * event, puts each in its canonical place (a row's step holds at most 246
+ * events).  The device form cannot know the total without a synchronise, so
+ * with capacity > 0 it ALLOCATES a staging buffer of capacity + 256 events
+ * (96 B each) from the stream-ordered pool, whatever the total: pass the
+ * sizing call's total as capacity, not a generous upper bound (a staging
+ * buffer that cannot be allocated is PXB_E_OOM).  The host form does so: it
+ * allocates min(total, capacity) events on the device.                        */
+#define PXB_EVT_ACCEPTOR 0u
+#define PXB_EVT_PROPOSER 1u
+#define PXB_EVT_HANDLED          0u
+#define PXB_EVT_DISCARDED_DEAD   1u   /* acceptor dead (after a panic): no handler ran  */
+#define PXB_EVT_DISCARDED_ISOL   2u   /* acceptor alive but inside its isolation window */
+#define PXB_EVT_PEER_TICK     0xFFu
+typedef struct pxb_trace_event {      /* 96 B, 16-byte aligned, no implicit padding */
+  uint32_t step;
+  uint8_t  actor;            /* PXB_EVT_ACCEPTOR / PXB_EVT_PROPOSER                          */
+  uint8_t  index;            /* a, or p                                                      */
+  uint8_t  peer;             /* the sender: p for an acceptor event, a for a proposer event, */
+                             /* PXB_EVT_PEER_TICK for a Tick                                 */
+  uint8_t  fate;             /* PXB_EVT_HANDLED / _DISCARDED_*                               */
+  uint32_t n_out;            /* messages the handler produced: 0..1 (acceptor), 0..2 (proposer) */
+  uint32_t reserved;         /* 0                                                            */
+  pxb_msg  in;               /* the message handled                                          */
+  pxb_msg  out[2];           /* produced messages; unused entries all 0                      */
+  union {                    /* the actor's state AFTER the handler; 32 B, unused bytes 0    */
+    struct { pxb_acceptor_rec rec; uint32_t log_digest; } acc;
+    pxb_trace_prop prop;
+  } after;
+} pxb_trace_event;
+int pxb_trace_events_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                            const pxb_trace_sel* sel, pxb_trace_event* d_events, uint64_t capacity,
+                            uint64_t* d_offsets, uint32_t* d_status, pxb_result* d_results, void* stream);
+int pxb_trace_events(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                     const pxb_trace_sel* sel, pxb_trace_event* events, uint64_t capacity, uint64_t* offsets,
+                     uint32_t* status, pxb_result* results, uint64_t* n_events);
+
 /* ---- batched shrinker (additive to ABI 5, found by symbol like the queries) ----
  * Many failing schedules reduced to 1-minimal fault sets at once, everything on
  * the device (docs/SEMANTICS.md §11).  Row i of d_rows (fully explicit rows, as
