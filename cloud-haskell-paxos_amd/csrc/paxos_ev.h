@@ -189,6 +189,9 @@ struct Shape {
 //   broadcast payload   x [11:0] | z [13:12] | kind [15:14]
 //   acceptor word       t_max [11:0] | t_store [23:12] | val [25:24] | dead [26] | log_len [31:27]
 //   window              c0 [15:0] | c1 [31:16]  (clamped to 4096: steps are < 4095)
+//   broadcast counters  (P <= 2) proposer 0 [15:0] | proposer 1 [31:16], one word for the
+//                       broadcasts sent (nsp), one for those queued (bcp: ring slot = low bits)
+//   pending queue       entry i (5 bits at 5i): ring slot [2:0] | proposer [4:3]; 0 above pq_len
 // Slim (SL, layout 5: the 4-entry layout on the 8-step wheel for runs of at
 // most 512 steps, BASELINE config 5): the reply seqs are bytes in registers
 // (a 256th reply on one link bails), 4 broadcast ring slots per proposer, and
@@ -366,8 +369,22 @@ struct EvLane : Src {
   uint32_t skew[PM];                  // the (next) Tick step of each proposer
   uint32_t tk_end[PM];                // LG: its last Tick step
   uint32_t tper;                      // LG: steps between Ticks
-  uint32_t nsent[PM];                 // broadcasts of p whose copies have started (request-link seq)
-  uint32_t bnext[PM];                 // next broadcast-ring slot
+  // Per-proposer broadcast counters.  Up to two proposers (CPK): 16-bit
+  // fields of one word each, field p at bit 16 p -- a read is one bit-field
+  // extract at a shifted offset, an update one shifted add, no one-hot select
+  // and put (round 8: main path -13 instructions on the tight layout, 3 VGPRs
+  // fewer).  A proposer makes at most three broadcasts per ticket value
+  // (AskForTicket, Propose, Execute) and tickets stay <= step_cap <= 4095
+  // here (SEMANTICS §6, ev_layouts.h MAX_STEP_CAP): under 12,288 broadcasts,
+  // so a field never carries into its neighbour.  Three proposers keep a word
+  // each, as before (three fields need a 64-bit word: not tried).
+  //   nsp / nsent[p]   broadcasts of p whose copies have all gone (the request links' Philox seq)
+  //   bcp              broadcasts of p queued so far: the next ring slot is its low bits
+  //   bnext[p]         (PM = 3) the next ring slot itself
+  static constexpr bool CPK = PM <= 2;
+  uint32_t nsp, bcp;
+  uint32_t nsent[CPK ? 1 : PM];
+  uint32_t bnext[CPK ? 1 : PM];
   // ring-slot reference counts, 4-bit nibbles: one 32- or 64-bit word for
   // every proposer when they fit (nibble p * BR + slot: an add, no one-hot
   // select), else a word each
@@ -497,6 +514,27 @@ struct EvLane : Src {
   __host__ __device__ __forceinline__ void ref_add(uint32_t q, uint32_t k, uint32_t d) {
     if constexpr (RPK) refp += (ref_t)(typename std::make_signed<ref_t>::type)(int32_t)d << (4u * (q * (uint32_t)S::BR + k));
     else put(refc, q, get(refc, q) + (d << (4u * k)));
+  }
+
+  // the broadcast counters of proposer q (CPK: its 16-bit field; one proposer: the word)
+  __host__ __device__ static __forceinline__ uint32_t fld_sh(uint32_t q) { return PM == 1 ? 0u : q << 4; }
+  __host__ __device__ __forceinline__ uint32_t nsent_of(uint32_t q) const {
+    if constexpr (CPK) return PM == 1 ? nsp : (nsp >> fld_sh(q)) & 0xFFFFu;
+    else return get(nsent, q);
+  }
+  // (ck: nsent_of(q); d: 1 or 0)
+  __host__ __device__ __forceinline__ void nsent_add(uint32_t q, uint32_t ck, uint32_t d) {
+    if constexpr (CPK) nsp += d << fld_sh(q);
+    else put(nsent, q, ck + d);
+  }
+  __host__ __device__ __forceinline__ uint32_t bslot_of(uint32_t q) const {
+    if constexpr (CPK) return (bcp >> fld_sh(q)) & (S::BR - 1u);
+    else return get(bnext, q);
+  }
+  // (slot0: bslot_of(q); nb: 0, 1 or 2 broadcasts queued)
+  __host__ __device__ __forceinline__ void bslot_add(uint32_t q, uint32_t slot0, uint32_t nb) {
+    if constexpr (CPK) bcp += nb << fld_sh(q);
+    else put(bnext, q, (slot0 + nb) & (S::BR - 1u));
   }
 
   // a value as the reference's command code (id << 24) | t (SEMANTICS §2)
@@ -668,7 +706,8 @@ struct EvLane : Src {
       const int32_t lt = (int32_t)(((uint32_t)p < P) ? tk_end[p] : 0u);
       last_tick = (lt > last_tick) ? lt : last_tick;
       pw0[p] = pw1[p] = pw2[p] = 0u;               // ticket 0, Idle, no command (Client.hs:90-95)
-      nsent[p] = bnext[p] = 0u;
+      nsent[CPK ? 0 : p] = bnext[CPK ? 0 : p] = 0u;
+      nsp = bcp = 0u;
       refc[RPK ? 0 : p] = 0u;
       refp = 0u;
     }
@@ -737,7 +776,8 @@ struct EvLane : Src {
     const bool first = ex & (dval == 0u);             // the decided value: first Execute (Client.hs:178)
     dval = first ? val : dval;
     dtick = first ? x0 : dtick;
-    const uint32_t slot0 = get(bnext, q), slot1 = (slot0 + 1u) & (S::BR - 1u);
+    // (slot1 from slot0's register: LLVM otherwise extracted the field a second time)
+    const uint32_t slot0 = CPK ? opaque(bslot_of(q)) : bslot_of(q), slot1 = (slot0 + 1u) & (S::BR - 1u);
     // a ring slot still referenced by a queued copy
     // (non-short-circuit: || here became two exec-mask branches)
     bailed = bailed | (p0 & (ref_nib(q, slot0) != 0u)) | (p1 & (ref_nib(q, slot1) != 0u));
@@ -767,10 +807,13 @@ struct EvLane : Src {
       m.st16h(w0a, h0a, p0 ? x0 | (z0 << 12) | (kind0 << 14) : o0);
       m.st16h(w1a, h1a, p1 ? x1 | (ASK << 14) : o1);
     }
-    pq |= (p0 ? ((q << 3) | slot0) << (5u * pq_len) : 0u) | (p1 ? ((q << 3) | slot1) << (5u * pq_len + 5u) : 0u);
+    // (both 5-bit entries as one 10-bit value, q in bits 3 and 8, cut to the
+    // nb entries made -- p1 only with p0 -- and shifted to the queue's end once)
     const uint32_t nb = (p0 ? 1u : 0u) + (p1 ? 1u : 0u);
+    const uint32_t ent2 = u24(q) * 0x108u + (slot0 | (slot1 << 5));
+    pq |= (ent2 & ((1u << (5u * nb)) - 1u)) << (5u * pq_len);
     pq_len += nb;
-    put(bnext, q, (slot0 + nb) & (S::BR - 1u));
+    bslot_add(q, slot0, nb);
   }
 
   // the next copy of the oldest pending broadcast, on link cp -> ca (Philox
@@ -795,7 +838,7 @@ struct EvLane : Src {
     const bool csnd = act & !isR & (pq_len != 0u);
     const uint32_t ce = pq & 31u;
     const uint32_t cp = ce >> 3, cslot = ce & 7u, ca = acur;
-    const uint32_t ck = get(nsent, cp);
+    const uint32_t ck = nsent_of(cp);
     {
       const uint32_t a1 = acur + 1u;
       const bool wrap = csnd & (a1 == (uint32_t)N);
@@ -804,7 +847,7 @@ struct EvLane : Src {
       pq_len -= wrap ? 1u : 0u;
       if constexpr (CARRY2) pqo -= (wrap & (pqo != 0u)) ? 1u : 0u;
       else pqo = pqo & !wrap;
-      put(nsent, cp, ck + (wrap ? 1u : 0u));
+      nsent_add(cp, ck, wrap ? 1u : 0u);
     }
     const bool snd = isR | csnd;
     PXB_EV_PROBE(EVP_SEND1, snd);
@@ -926,7 +969,7 @@ struct EvLane : Src {
   // its proposer, tag = (proposer, acceptor))
   __host__ __device__ __forceinline__ uint2 copy_ctr() const {
     const uint32_t cp = (pq & 31u) >> 3;
-    return make_uint2(get(nsent, cp), (1u << 24) | (cp << 8) | acur);
+    return make_uint2(nsent_of(cp), (1u << 24) | (cp << 8) | acur);
   }
   __host__ __device__ __forceinline__ void copy_send(const EvParams& kp, bool act, const uint4& w) {
     // the broadcast's own step: s, or s - 1 for one carried over by end_op
@@ -936,7 +979,7 @@ struct EvLane : Src {
     PXB_EV_PROBE(EVP_COPY, snd);
     const uint32_t ce = pq & 31u;
     const uint32_t cp = ce >> 3, cslot = ce & 7u, ca = acur;
-    const uint32_t ck = get(nsent, cp);
+    const uint32_t ck = nsent_of(cp);
     {                                                // (branch-free: selects, no exec-mask branches)
       const uint32_t a1 = acur + 1u;
       const bool wrap = snd & (a1 == (uint32_t)N);    // the broadcast's last copy
@@ -945,7 +988,7 @@ struct EvLane : Src {
       pq_len -= wrap ? 1u : 0u;
       if constexpr (CARRY2) pqo -= (wrap & (pqo != 0u)) ? 1u : 0u;
       else pqo = pqo & !wrap;
-      put(nsent, cp, ck + (wrap ? 1u : 0u));
+      nsent_add(cp, ck, wrap ? 1u : 0u);
     }
     // (w: the draw of copy_ctr() taken before this call)
     const bool ok = !(kLossy & lossy & (w.x <= loss_m1));
@@ -1056,7 +1099,8 @@ struct EvLane : Src {
     // entries, length and reply seq, adjusted in place)
     const uint32_t rq2 = ((wq & ((1u << S::QL) - 1u)) >> S::EB) + ((wq & ~((1u << S::QL) - 1u)) - (1u << S::QL));
     const bool keep = (len > 1u) & (((wq >> (S::EB + S::SB)) & DM) == (s4 & DM));   // the next entry due now too
-    acc_mask = (acc & !keep) ? (acc_mask & ~(1u << L)) : acc_mask;
+    // (bit L, the lowest of ready, is set in acc_mask whenever acc: an XOR clears it)
+    acc_mask ^= ((acc & !keep) ? 1u : 0u) << L;
     uint32_t kind, x, z;
     if constexpr (LG) {
       const uint32_t w32 = m.ld(S::BRING + p * S::BR + bslot);
@@ -1195,17 +1239,20 @@ struct EvLane : Src {
   __host__ __device__ __forceinline__ bool prop_ready() const { return in_mask != 0u && pq_len + 2u <= PQ_CAP; }
   __host__ __device__ __forceinline__ void prop_op(const EvParams& kp, bool act) {
     const uint32_t s4 = (uint32_t)s & 15u;
-    const bool pin = act & (in_mask != 0u) & (pq_len + 2u <= PQ_CAP);
+    const bool pin = act & (in_mask != 0u) & (pq_len <= PQ_CAP - 2u);
     PXB_EV_PROBE(EVP_PROP, pin);
     {
-      const uint32_t j = pin ? ctz32(in_mask) : 0u;
+      // (pin: in_mask != 0, so the bare count, without ctz32's test for 0)
+      const uint32_t j = pin ? (uint32_t)__builtin_ctz(in_mask) : 0u;
       // (SP: bit j is response link j; j / N as a multiply-shift, exact for j < 2^10)
       const uint32_t q = SP ? (j * ((65536u + N - 1u) / N)) >> 16 : j / (uint32_t)(N + 1);
       const uint32_t r = SP ? 1u : j - mulc<N + 1>(q);
       const bool resp = pin & (r != 0u);
       const uint32_t ra = r - 1u;
       const uint32_t Lr = SP ? j : mulc<N>(q) + (resp ? ra : 0u);
-      const uint32_t rr = rsp_ld(Lr);
+      // (RH: the halfword as a 32-bit value -- the load zero-extends; left a
+      // 16-bit value for the store-back select, LLVM masked it for every other use)
+      const uint32_t rr = S::RH ? opaque(rsp_ld(Lr)) : rsp_ld(Lr);
       const uint32_t rlen = (rr >> S::RL) & RLM;
       // (RH: with one entry, nk is the sentinel: rkeep tests for a second entry)
       const uint32_t k = rr & IM, nk = (rr >> S::IB) & IM;
@@ -1221,7 +1268,8 @@ struct EvLane : Src {
       rsp_st(Lr, resp ? popped : rr);                // (popped: entries down one, length - 1)
       const bool nnow = nkc ? ((nk & 7u) == (s4 & 7u)) : (((pn >> 26) & 15u) == s4);
       const bool rkeep = resp & (S::RH ? rr >= (1u << (2 * S::IB)) : S::RZ ? nk != 0u : rlen > 1u) & nnow;
-      in_mask = (pin & !rkeep) ? (in_mask & ~(1u << j)) : in_mask;
+      // (bit j is set whenever pin: clearing it is an XOR of the shifted predicate)
+      in_mask ^= ((pin & !rkeep) ? 1u : 0u) << j;
       const uint32_t rkind = pe >> 30, px = pe & 0xFFFu, py = (pe >> 12) & 0xFFFu;
       const uint32_t kz = k - (uint32_t)S::POOLB_SHIFT;   // (the pool index of entry k)
       const uint32_t pz = LG ? m.ld16h(S::POOLZ + ((kz >> 1) & 31u), kz & 1u) : (pe >> 24) & 3u;
@@ -1249,9 +1297,15 @@ struct EvLane : Src {
         const bool maj1 = K >= maj;                                      // acks + 1 > maj
         const bool o_take = (MV == 0u) | ((pz != 0u) & !(MT >= py));     // MostRecent (Common.hs:61-65)
         const uint32_t mv = o_take ? pz : MV;
-        const bool o_maj = o_go & maj1, s_maj = s_go & maj1;
+        // (logical &&, on purpose: with & LLVM carried o_go, s_go, maj1 and all
+        // that derives from them as 0 / 1 integers, a v_cndmask each and a v_cmp
+        // back to a lane mask per use; these stay lane masks, no branch appears.
+        // Round 8, tight layout: 10 VALU fewer for 3 SALU more)
+        const bool o_maj = o_go && maj1, s_maj = s_go && maj1;
         const uint32_t PDb = w0 & (1u << 30);
-        const bool sPD = s_maj & (PDb != 0u);                            // Execute + restart (:185)
+        // (the pending bit as one compare of the masked word: folded into the
+        // other predicates as a bit, LLVM carried them all as 0 / 1 integers)
+        const bool sPD = s_maj & (opaque(PDb) != 0u);                    // Execute + restart (:185)
         const bool ask = t_go | h_go;
         const bool restart = ask | sPD;                                  // -> Round1 with a new ticket
         const uint32_t Tn = (h_go ? px : T) + (restart ? 1u : 0u);
@@ -1346,7 +1400,7 @@ struct EvLane : Src {
   __host__ __device__ __forceinline__ uint32_t msgs_sent() const {
     uint32_t b = 0u;
 #pragma unroll
-    for (int p = 0; p < PM; ++p) b += nsent[p];
+    for (int p = 0; p < PM; ++p) b += nsent_of((uint32_t)p);
     return msgs + b * (uint32_t)N;
   }
 

@@ -241,7 +241,7 @@ __host__ __device__ __forceinline__ void script_sent(const Lane& L, uint16_t* ou
   constexpr uint32_t P = Lane::S::PM, N = Lane::S::N;
   for (uint32_t p = 0; p < P; ++p)
     for (uint32_t a = 0; a < N; ++a) {
-      out[p * N + a] = (uint16_t)(p < L.P ? L.nsent[p] : 0u);
+      out[p * N + a] = (uint16_t)(p < L.P ? L.nsent_of(p) : 0u);
       out[(P + p) * N + a] = (uint16_t)(p < L.P ? L.m.ld16(Lane::S::RSEQ, a * P + p) : 0u);
     }
 }

@@ -23,7 +23,7 @@ CUS = 256
 PEAK_CLOCK_HZ = 2.4e9
 VALU_PER_CU_CYCLE = 2.0
 KERNEL_TAGS = ("paxos_ev_kernel", "paxos_ff1_kernel", "paxos_ffp_kernel",
-               "paxos_batch_kernel", "finalize_kernel")
+               "paxos_batch_kernel", "paxos_win_kernel", "finalize_kernel")
 # kernels a profiled bench command may also run that are not part of a step
 # (torch's own fills and copies, the wire codec's passes)
 IGNORED = ("elementwise", "fill", "copy", "memset", "Memset", "Memcpy", "tile_sum", "encode_kernel",
