@@ -1,8 +1,9 @@
 // host_util.h — what the entry points of the tool families (trace batch,
 // scripted schedules, shrinker, explorer, query, wire codec) share on the host
-// side: the error mapping, the scratch padding, the device checks, the per-call
-// scratch pool's declaration and the uint32 -> uint64 widening iterator that
-// hipCUB's exclusive sums read counts through.  Internal to the library's
+// side on top of host_stage.h (the error mapping and the host buffers' staging):
+// the scratch padding, the device checks, the per-call scratch pool's
+// declaration and the uint32 -> uint64 widening iterator that hipCUB's
+// exclusive sums read counts through.  Internal to the library's
 // .hip units; a unit built per proposer count includes it only where its entry
 // points are (hipCUB is slow to compile).
 #pragma once
@@ -12,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/paxos_batch.h"
+#include "host_stage.h"
 
 namespace pxw {
 // paxos_wire.hip: per-call scratch from the device's stream-ordered pool
@@ -24,13 +26,8 @@ namespace host {
 
 constexpr uint64_t MAX_COUNT = 1ull << 30;        // rows, ids or parents of one call
 
-inline int hip_fail(hipError_t e) { return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP; }
 inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-inline int device_count() {
-  int n = 0;
-  return (hipGetDeviceCount(&n) != hipSuccess) ? 0 : n;
-}
 // the current device (< 64: pxw::scratch keeps one pool per device in an array of 64)
 inline int current_device(int* dev) {
   return (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= 64) ? PXB_E_NODEV : PXB_OK;

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "host_stage.h"
 #include "paxos_ev_kernel.h"
 #include "paxos_ff1.h"
 #include "paxos_ffp.h"
@@ -317,10 +318,9 @@ struct EvLists {
 static EvLists g_lists[64][EV_LIST_STREAMS];
 static int g_nlists[64], g_lnext[64];
 
-static int hip_fail(hipError_t e) {
-  g_last_hip = (int)e;
-  return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP;
-}
+// (host_stage.h: every unit's hip_fail records here)
+void host::set_last_hip_error(int e) { g_last_hip = e; }
+using host::hip_fail;
 #define HIPCHK(x)                                   \
   do {                                              \
     hipError_t _e = (x);                            \
@@ -912,35 +912,21 @@ int pxb_run(const pxb_config* cfg, pxb_result* out, uint32_t* log_digest, pxb_ac
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
   const uint64_t n = cfg->n_instances, N = cfg->n_acceptors;
-  pxb_result* d_out = nullptr;
-  uint32_t* d_dig = nullptr;
-  pxb_acceptor_rec* d_acc = nullptr;
-  int64_t* d_tot = nullptr;
-  hipError_t e = hipSuccess;
-  rc = PXB_OK;
-  do {
-    if (out && n && (e = hipMalloc(&d_out, n * sizeof(pxb_result))) != hipSuccess) break;
-    if (log_digest && n && (e = hipMalloc(&d_dig, n * N * sizeof(uint32_t))) != hipSuccess) break;
-    if (acc && n && (e = hipMalloc(&d_acc, n * N * sizeof(pxb_acceptor_rec))) != hipSuccess) break;
-    if ((e = hipMalloc(&d_tot, PXB_NCOUNTERS * sizeof(int64_t))) != hipSuccess) break;
-    if ((e = hipMemset(d_tot, 0, PXB_NCOUNTERS * sizeof(int64_t))) != hipSuccess) break;
-    rc = pxb_run_device(cfg, d_out, d_dig, d_acc, d_tot, nullptr);
-    if (rc) break;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-    if (out && n && (e = hipMemcpy(out, d_out, n * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (log_digest && n &&
-        (e = hipMemcpy(log_digest, d_dig, n * N * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (acc && n && (e = hipMemcpy(acc, d_acc, n * N * sizeof(pxb_acceptor_rec), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-    if (totals && (e = hipMemcpy(totals->c, d_tot, PXB_NCOUNTERS * sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-  } while (0);
-  if (e != hipSuccess) rc = hip_fail(e);
-  if (d_out) (void)hipFree(d_out);
-  if (d_dig) (void)hipFree(d_dig);
-  if (d_acc) (void)hipFree(d_acc);
-  if (d_tot) (void)hipFree(d_tot);
-  return rc;
+  StagePlan plan;                                 // results | digests | acceptor records | totals: one block
+  const StageRegion r_out = plan.add(sizeof(pxb_result), out ? n : 0);
+  const StageRegion r_dig = plan.add(N * sizeof(uint32_t), log_digest ? n : 0);
+  const StageRegion r_acc = plan.add(N * sizeof(pxb_acceptor_rec), acc ? n : 0), r_tot = plan.add(sizeof(int64_t), PXB_NCOUNTERS);
+  host::Staging S(plan);
+  S.zero(r_tot);
+  if (S.ok())
+    S.note(pxb_run_device(cfg, S.ptr<pxb_result>(r_out), S.ptr<uint32_t>(r_dig), S.ptr<pxb_acceptor_rec>(r_acc),
+                          S.ptr<int64_t>(r_tot), nullptr));
+  S.sync();
+  S.down(r_out, out, n);
+  S.down(r_dig, log_digest, n);
+  S.down(r_acc, acc, n);
+  S.down(r_tot, totals ? totals->c : nullptr, PXB_NCOUNTERS);
+  return S.finish();
 }
 
 extern "C" int pxb_query_validate(const pxb_query* q, const void* ids, uint64_t capacity, const void* n_matches,
@@ -959,47 +945,35 @@ int pxb_sweep(const pxb_config* cfg, const pxb_query* q, uint64_t* ids, pxb_resu
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
   const uint64_t n = cfg->n_instances, chunk = hooks().sweep_chunk;
   const uint64_t cap = std::min(capacity, n);            // (no more matches than instances)
-  const size_t bs = q->n_bins_steps * sizeof(int64_t), br = q->n_bins_rounds * sizeof(int64_t);
-  pxb_result *d_res = nullptr, *d_matched = nullptr;
-  uint64_t *d_ids = nullptr, *d_cur = nullptr;
-  int64_t *d_hs = nullptr, *d_hr = nullptr, *d_tot = nullptr;
-  hipError_t e = hipSuccess;
-  do {
-    if (n && (e = hipMalloc(&d_res, std::min(n, chunk) * sizeof(pxb_result))) != hipSuccess) break;
-    if (cap && (e = hipMalloc(&d_ids, cap * sizeof(uint64_t))) != hipSuccess) break;
-    if (cap && matched && (e = hipMalloc(&d_matched, cap * sizeof(pxb_result))) != hipSuccess) break;
-    if (bs && (e = hipMalloc(&d_hs, bs)) != hipSuccess) break;
-    if (br && (e = hipMalloc(&d_hr, br)) != hipSuccess) break;
-    if ((e = hipMalloc(&d_cur, sizeof(uint64_t))) != hipSuccess) break;
-    if ((e = hipMalloc(&d_tot, PXB_NCOUNTERS * sizeof(int64_t))) != hipSuccess) break;
-    if ((e = hipMemset(d_cur, 0, sizeof(uint64_t))) != hipSuccess) break;
-    if ((e = hipMemset(d_tot, 0, PXB_NCOUNTERS * sizeof(int64_t))) != hipSuccess) break;
-    if (bs && (e = hipMemset(d_hs, 0, bs)) != hipSuccess) break;
-    if (br && (e = hipMemset(d_hr, 0, br)) != hipSuccess) break;
-    pxb_config c = *cfg;
-    for (uint64_t k = 0, nk = sweep_n_chunks(n, chunk); k < nk && rc == PXB_OK; ++k) {
-      const SweepChunk ch = sweep_chunk_at(cfg->first_instance, n, chunk, k);
-      c.first_instance = ch.first;
-      c.n_instances = ch.count;
-      if ((rc = pxb_run_device(&c, d_res, nullptr, nullptr, d_tot, nullptr)) != PXB_OK) break;
-      rc = pxb_query_device(d_res, ch.first, ch.count, q, d_ids, d_matched, cap, d_cur, d_hs, d_hr, nullptr);
-    }
-    // (also after a failed chunk: nothing is freed under queued work)
-    if ((e = hipDeviceSynchronize()) != hipSuccess || rc != PXB_OK) break;
-    if ((e = hipMemcpy(n_matches, d_cur, sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    const uint64_t nw = std::min(*n_matches, cap);
-    if (nw && (e = hipMemcpy(ids, d_ids, nw * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (nw && matched && (e = hipMemcpy(matched, d_matched, nw * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-    if (bs && (e = hipMemcpy(hist_steps, d_hs, bs, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (br && (e = hipMemcpy(hist_rounds, d_hr, br, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (totals && (e = hipMemcpy(totals->c, d_tot, PXB_NCOUNTERS * sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-  } while (0);
-  if (e != hipSuccess) rc = hip_fail(e);
-  for (void* p : {(void*)d_res, (void*)d_ids, (void*)d_matched, (void*)d_hs, (void*)d_hr, (void*)d_cur, (void*)d_tot})
-    if (p) (void)hipFree(p);
-  return rc;
+  const uint64_t nh = q->n_bins_steps, nr = q->n_bins_rounds;
+  StagePlan plan;                                 // a chunk's results | ids | matched | bins | bins | cursor | totals
+  const StageRegion r_res = plan.add(sizeof(pxb_result), std::min(n, chunk));
+  const StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_matched = plan.add(sizeof(pxb_result), matched ? cap : 0);
+  const StageRegion r_hs = plan.add(sizeof(int64_t), nh), r_hr = plan.add(sizeof(int64_t), nr);
+  const StageRegion r_cur = plan.add(sizeof(uint64_t), 1), r_tot = plan.add(sizeof(int64_t), PXB_NCOUNTERS);
+  host::Staging S(plan);
+  S.zero(r_cur), S.zero(r_tot), S.zero(r_hs), S.zero(r_hr);
+  pxb_config c = *cfg;
+  for (uint64_t k = 0, nk = sweep_n_chunks(n, chunk); k < nk && S.ok(); ++k) {
+    const SweepChunk ch = sweep_chunk_at(cfg->first_instance, n, chunk, k);
+    c.first_instance = ch.first;
+    c.n_instances = ch.count;
+    pxb_result* const d_res = S.ptr<pxb_result>(r_res);
+    S.note(pxb_run_device(&c, d_res, nullptr, nullptr, S.ptr<int64_t>(r_tot), nullptr));
+    if (S.ok())
+      S.note(pxb_query_device(d_res, ch.first, ch.count, q, S.ptr<uint64_t>(r_ids), S.ptr<pxb_result>(r_matched), cap,
+                              S.ptr<uint64_t>(r_cur), S.ptr<int64_t>(r_hs), S.ptr<int64_t>(r_hr), nullptr));
+  }
+  // (after a failed chunk, finish() waits: nothing is freed under queued work)
+  S.sync();
+  S.down(r_cur, n_matches, 1);
+  const uint64_t nw = S.ok() ? std::min(*n_matches, cap) : 0;
+  S.down(r_ids, ids, nw);
+  S.down(r_matched, matched, nw);
+  S.down(r_hs, hist_steps, nh);
+  S.down(r_hr, hist_rounds, nr);
+  S.down(r_tot, totals ? totals->c : nullptr, PXB_NCOUNTERS);
+  return S.finish();
 }
 
 static int run_hook(bool acceptor, void* st, size_t st_bytes, uint32_t n_acc, const pxb_msg* in, pxb_msg* out,
@@ -1008,33 +982,28 @@ static int run_hook(bool acceptor, void* st, size_t st_bytes, uint32_t n_acc, co
   if (count == 0) return PXB_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
-  void *d_st = nullptr, *d_in = nullptr, *d_out = nullptr, *d_nb = nullptr;
-  hipError_t e = hipSuccess;
-  do {
-    if ((e = hipMalloc(&d_st, st_bytes * count)) != hipSuccess) break;
-    if ((e = hipMalloc(&d_in, sizeof(pxb_msg) * count)) != hipSuccess) break;
-    if ((e = hipMalloc(&d_out, sizeof(pxb_msg) * out_n * count)) != hipSuccess) break;
-    if (!acceptor && (e = hipMalloc(&d_nb, sizeof(uint32_t) * count)) != hipSuccess) break;
-    if ((e = hipMemcpy(d_st, st, st_bytes * count, hipMemcpyHostToDevice)) != hipSuccess) break;
-    if ((e = hipMemcpy(d_in, in, sizeof(pxb_msg) * count, hipMemcpyHostToDevice)) != hipSuccess) break;
+  StagePlan plan;                                 // states | messages in | messages out | broadcast counts
+  const StageRegion r_st = plan.add(st_bytes, count), r_in = plan.add(sizeof(pxb_msg), count);
+  const StageRegion r_out = plan.add(sizeof(pxb_msg) * out_n, count);
+  const StageRegion r_nb = plan.add(sizeof(uint32_t), acceptor ? 0 : count);
+  host::Staging S(plan);
+  S.up(r_st, st, count);
+  S.up(r_in, in, count);
+  if (S.ok()) {
     const unsigned grid = (count + 255) / 256;
     if (acceptor)
-      hipLaunchKernelGGL(acceptor_hook_kernel, dim3(grid), dim3(256), 0, 0, (pxb_acceptor_rec*)d_st,
-                         (const pxb_msg*)d_in, (pxb_msg*)d_out, count);
+      hipLaunchKernelGGL(acceptor_hook_kernel, dim3(grid), dim3(256), 0, 0, S.ptr<pxb_acceptor_rec>(r_st),
+                         S.ptr<const pxb_msg>(r_in), S.ptr<pxb_msg>(r_out), count);
     else
-      hipLaunchKernelGGL(proposer_hook_kernel, dim3(grid), dim3(256), 0, 0, (pxb_proposer_rec*)d_st, n_acc,
-                         (const pxb_msg*)d_in, (pxb_msg*)d_out, (uint32_t*)d_nb, count);
-    if ((e = hipGetLastError()) != hipSuccess) break;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-    if ((e = hipMemcpy(st, d_st, st_bytes * count, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if ((e = hipMemcpy(out, d_out, sizeof(pxb_msg) * out_n * count, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (!acceptor && (e = hipMemcpy(nb, d_nb, sizeof(uint32_t) * count, hipMemcpyDeviceToHost)) != hipSuccess) break;
-  } while (0);
-  if (d_st) (void)hipFree(d_st);
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (d_nb) (void)hipFree(d_nb);
-  return (e == hipSuccess) ? PXB_OK : hip_fail(e);
+      hipLaunchKernelGGL(proposer_hook_kernel, dim3(grid), dim3(256), 0, 0, S.ptr<pxb_proposer_rec>(r_st), n_acc,
+                         S.ptr<const pxb_msg>(r_in), S.ptr<pxb_msg>(r_out), S.ptr<uint32_t>(r_nb), count);
+    S.note(hipGetLastError());
+  }
+  S.sync();
+  S.down(r_st, st, count);
+  S.down(r_out, out, count);
+  S.down(r_nb, nb, count);
+  return S.finish();
 }
 
 int pxb_acceptor_handle(pxb_acceptor_rec* states, const pxb_msg* req, pxb_msg* reply, uint32_t count) {

@@ -138,12 +138,10 @@ static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uin
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 
-static size_t scan_bytes(uint64_t count, hipStream_t st) {
-  size_t need = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
-                                       (int64_t)(count + 1), st) != hipSuccess)
-    return (size_t)-1;
-  return need;
+static hipError_t scan_bytes(uint64_t count, hipStream_t st, size_t* need) {
+  *need = 0;
+  return hipcub::DeviceScan::ExclusiveSum(nullptr, *need, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
+                                          (int64_t)(count + 1), st);
 }
 
 }  // namespace pxev
@@ -167,8 +165,8 @@ int pxb_trace_events_device(const pxb_config* cfg, const uint8_t* d_rows, uint64
     const hipError_t e = hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st);
     return (e == hipSuccess) ? PXB_OK : hip_fail(e);
   }
-  size_t need = scan_bytes(count, st);
-  if (need == (size_t)-1) return PXB_E_HIP;
+  size_t need = 0;
+  if (hipError_t e = scan_bytes(count, st, &need)) return hip_fail(e);
   const bool write = capacity && d_events;
   if (write && capacity > (~(uint64_t)0 >> 8) / sizeof(pxb_trace_event)) return PXB_E_INVAL;
   const uint64_t room = capacity + EVT_SEG_MAX;
@@ -219,7 +217,7 @@ int pxb_trace_events_device(const pxb_config* cfg, const uint8_t* d_rows, uint64
   return (e == hipSuccess) ? PXB_OK : hip_fail(e);
 }
 
-// the HOST-buffer form: device copies of the buffers around the device form
+// the HOST-buffer form: device copies of the buffers (host_stage.h) around the device form
 int pxb_trace_events(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
                      const pxb_trace_sel* sel, pxb_trace_event* events, uint64_t capacity, uint64_t* offsets,
                      uint32_t* status, pxb_result* results, uint64_t* n_events) {
@@ -227,44 +225,14 @@ int pxb_trace_events(const pxb_config* cfg, const uint8_t* rows, uint64_t count,
   evt_ptr fn = nullptr;
   if (int rc = validate(cfg, rows, count, depth, sel, events, capacity, offsets, &fn)) return rc;
   if (device_count() == 0) return PXB_E_NODEV;
-  if (count == 0) {
-    offsets[0] = 0;
-    if (n_events) *n_events = 0;
-    return PXB_OK;
-  }
-  const size_t rows_n = (size_t)(count * script_stride(cfg->n_proposers, cfg->n_acceptors, depth));
-  const size_t rows_b = pad256(rows_n), off_b = pad256((count + 1) * sizeof(uint64_t));
-  const size_t st_b = pad256(count * sizeof(uint32_t)), res_b = pad256(count * sizeof(pxb_result));
-  char* buf = nullptr;                            // rows | offsets | status | results
-  pxb_trace_event* d_ev = nullptr;
-  hipError_t e = hipMalloc(&buf, rows_b + off_b + st_b + res_b);
-  if (e != hipSuccess) return hip_fail(e);
-  uint8_t* const d_rows = reinterpret_cast<uint8_t*>(buf);
-  uint64_t* const d_off = reinterpret_cast<uint64_t*>(buf + rows_b);
-  uint32_t* const d_st = reinterpret_cast<uint32_t*>(buf + rows_b + off_b);
-  pxb_result* const d_res = reinterpret_cast<pxb_result*>(buf + rows_b + off_b + st_b);
-  int rc = PXB_OK;
-  do {
-    if ((e = hipMemcpy(d_rows, rows, rows_n, hipMemcpyHostToDevice)) != hipSuccess) break;
-    // the sizing call, then (events to write) the call again with the events' buffer
-    rc = pxb_trace_events_device(cfg, d_rows, count, depth, sel, nullptr, 0, d_off, d_st, d_res, nullptr);
-    if (rc) break;
-    if ((e = hipMemcpy(offsets, d_off, (count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    const uint64_t total = offsets[count], m = total < capacity ? total : capacity;
-    if (m) {
-      if ((e = hipMalloc(&d_ev, m * sizeof(pxb_trace_event))) != hipSuccess) break;
-      rc = pxb_trace_events_device(cfg, d_rows, count, depth, sel, d_ev, m, d_off, d_st, d_res, nullptr);
-      if (rc) break;
-      if ((e = hipMemcpy(events, d_ev, m * sizeof(pxb_trace_event), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    }
-    if (status && (e = hipMemcpy(status, d_st, count * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (results && (e = hipMemcpy(results, d_res, count * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (n_events) *n_events = total;
-    e = hipDeviceSynchronize();
-  } while (0);
-  if (d_ev) (void)hipFree(d_ev);
-  (void)hipFree(buf);
-  return rc ? rc : (e == hipSuccess) ? PXB_OK : hip_fail(e);
+  // (both calls get the status and results buffers, whatever the caller asked for)
+  const auto call = [&](Staging&, const TraceBufs& d, pxb_trace_event* d_ev = nullptr, uint64_t m = 0) {
+    return pxb_trace_events_device(cfg, static_cast<uint8_t*>(d.in), count, depth, sel, d_ev, m, d.off, d.st, d.res,
+                                   nullptr);
+  };
+  pxb::StagePlan plan;                            // rows | offsets | status | results
+  return trace_two_call(plan, rows, script_stride(cfg->n_proposers, cfg->n_acceptors, depth), count, events, capacity,
+                        offsets, status, results, n_events, call, call);
 }
 
 }  // extern "C"

@@ -294,9 +294,9 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
 
   const uint64_t total = count * e.T, ntiles = (total + XBLOCK - 1) / XBLOCK;
   size_t scan_b = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
-                                       (int64_t)ntiles, st) != hipSuccess)
-    return PXB_E_HIP;
+  if (hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
+                                                      (int64_t)ntiles, st))
+    return hip_fail(e);
   // the call's scratch: list base | flag bytes | tile counts | tile offsets | scan
   const size_t bytes_b = pad256((size_t)total), cnt_b = pad256((size_t)(ntiles * 4u)), off_b = pad256((size_t)(ntiles * 8u));
   char* buf = nullptr;
@@ -368,37 +368,29 @@ int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint
   const uint64_t per = chunk / e.T ? chunk / e.T : 1u, m_max = per < count ? per : count;
   const uint64_t stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
   const uint64_t cap = capacity < count * e.T ? capacity : count * e.T;
-  const size_t rows_b = pad256((size_t)(m_max * stride)), ids_b = pad256((size_t)(cap * 8u));
-  const size_t cnt_b = pad256((size_t)(count * 48u)), st_b = pad256((size_t)(count * 4u));
-  char* buf = nullptr;                            // rows (one chunk) | cursor | ids | counts | status
-  hipError_t err = hipMalloc(&buf, rows_b + 256u + ids_b + cnt_b + st_b);
-  if (err != hipSuccess) return hip_fail(err);
-  uint8_t* const d_rows = reinterpret_cast<uint8_t*>(buf);
-  uint64_t* const d_n = reinterpret_cast<uint64_t*>(buf + rows_b);
-  uint64_t* const d_ids = reinterpret_cast<uint64_t*>(buf + rows_b + 256u);
-  uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(buf + rows_b + 256u + ids_b);
-  uint32_t* const d_st = reinterpret_cast<uint32_t*>(buf + rows_b + 256u + ids_b + cnt_b);
-  int rc = PXB_OK;
-  do {
-    if ((err = hipMemset(d_n, 0, 8u)) != hipSuccess) break;
-    for (uint64_t a = 0; a < count && rc == PXB_OK && err == hipSuccess; a += m_max) {
-      const uint64_t m = count - a < m_max ? count - a : m_max;
-      if ((err = hipMemcpy(d_rows, rows + a * stride, (size_t)(m * stride), hipMemcpyHostToDevice)) != hipSuccess) break;
-      rc = pxb_explore_device(cfg, d_rows, m, depth, space, a, cap ? d_ids : nullptr, cap, d_n,
-                              counts ? d_cnt + a * 12u : nullptr, status ? d_st + a : nullptr, nullptr);
-      // (the next chunk's rows overwrite these: wait for the kernels that read them)
-      if (rc == PXB_OK) err = hipStreamSynchronize(nullptr);
-    }
-    if (rc || err != hipSuccess) break;
-    if ((err = hipMemcpy(n_matches, d_n, 8u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    const uint64_t k = *n_matches < cap ? *n_matches : cap;
-    if (k && (err = hipMemcpy(ids, d_ids, (size_t)(k * 8u), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (counts && (err = hipMemcpy(counts, d_cnt, (size_t)(count * 48u), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (status && (err = hipMemcpy(status, d_st, (size_t)(count * 4u), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    err = hipDeviceSynchronize();
-  } while (0);
-  (void)hipFree(buf);
-  return rc ? rc : (err == hipSuccess) ? PXB_OK : hip_fail(err);
+  pxb::StagePlan plan;                            // rows (one chunk) | cursor | ids | counts | status
+  const pxb::StageRegion r_rows = plan.add(stride, m_max), r_n = plan.add(sizeof(uint64_t), 1);
+  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_cnt = plan.add(12u * sizeof(uint32_t), count);
+  const pxb::StageRegion r_st = plan.add(sizeof(uint32_t), count);
+  Staging S(plan);
+  S.zero(r_n);
+  uint32_t* const d_cnt = S.ptr<uint32_t>(r_cnt, counts);
+  uint32_t* const d_st = S.ptr<uint32_t>(r_st, status);
+  for (uint64_t a = 0; a < count && S.ok(); a += m_max) {
+    const uint64_t m = count - a < m_max ? count - a : m_max;
+    S.up(r_rows, rows + a * stride, m);
+    if (S.ok())
+      S.note(pxb_explore_device(cfg, S.ptr<uint8_t>(r_rows), m, depth, space, a, S.ptr<uint64_t>(r_ids), cap,
+                                S.ptr<uint64_t>(r_n), d_cnt ? d_cnt + a * 12u : nullptr, d_st ? d_st + a : nullptr,
+                                nullptr));
+    // (the next chunk's rows overwrite these: wait for the kernels that read them)
+    if (S.ok()) S.note(hipStreamSynchronize(nullptr));
+  }
+  S.down(r_n, n_matches, 1);
+  if (S.ok()) S.down(r_ids, ids, *n_matches < cap ? *n_matches : cap);
+  S.down(r_cnt, counts, count);
+  S.down(r_st, status, count);
+  return S.finish();
 }
 
 }  // extern "C"

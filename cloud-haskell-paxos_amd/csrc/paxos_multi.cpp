@@ -17,11 +17,14 @@
 #include <vector>
 
 #include "../../include/paxos_batch.h"
+#include "host_stage.h"
 #include "shard_runner.h"
 
 extern "C" bool multi_fail_injected(const char* phase, int g);   // paxos_batch.hip
 
 namespace {
+using pxb::host::hip_fail;
+using pxb::host::hip_rc;
 
 std::mutex g_comm_mu;
 // one pxb_run_multi at a time: concurrent calls would issue collectives on the
@@ -99,8 +102,15 @@ struct HipShards {
     int64_t* d_tot = nullptr;
     uint64_t lo = 0, m = 0;
     int64_t tot[PXB_NCOUNTERS] = {0};
+    int hip = 0;                     // the HIP code behind this device's failure (0: none, or not a HIP one)
   };
   std::vector<Dev> dv;
+
+  // a phase's code; a failure's HIP detail is in this worker thread's slot, which ends with the thread: keep it
+  int done(int g, int rc) {
+    if (rc) dv[g].hip = pxb_last_hip_error();
+    return rc;
+  }
 
   int setup(int g) {
     Dev& d = dv[g];
@@ -108,34 +118,32 @@ struct HipShards {
     d.lo = n * (uint64_t)g / (uint64_t)G;
     d.m = n * (uint64_t)(g + 1) / (uint64_t)G - d.lo;
     if (injected("setup", g)) return PXB_E_HIP;
-    if (hipSetDevice(g) != hipSuccess || hipStreamCreate(&d.st) != hipSuccess) return PXB_E_HIP;
-    if (hipMalloc(&d.d_tot, PXB_NCOUNTERS * sizeof(int64_t)) != hipSuccess) return PXB_E_OOM;
-    if (out && d.m && hipMalloc(&d.d_out, d.m * sizeof(pxb_result)) != hipSuccess) return PXB_E_OOM;
-    if (log_digest && d.m && hipMalloc(&d.d_dig, d.m * N * sizeof(uint32_t)) != hipSuccess) return PXB_E_OOM;
-    if (acc && d.m && hipMalloc(&d.d_acc, d.m * N * sizeof(pxb_acceptor_rec)) != hipSuccess) return PXB_E_OOM;
-    if (hipMemsetAsync(d.d_tot, 0, PXB_NCOUNTERS * sizeof(int64_t), d.st) != hipSuccess) return PXB_E_HIP;
-    return PXB_OK;
+    hipError_t e = hipSetDevice(g);
+    if (e == hipSuccess) e = hipStreamCreate(&d.st);
+    if (e == hipSuccess) e = hipMalloc(&d.d_tot, PXB_NCOUNTERS * sizeof(int64_t));
+    if (e == hipSuccess && out && d.m) e = hipMalloc(&d.d_out, d.m * sizeof(pxb_result));
+    if (e == hipSuccess && log_digest && d.m) e = hipMalloc(&d.d_dig, d.m * N * sizeof(uint32_t));
+    if (e == hipSuccess && acc && d.m) e = hipMalloc(&d.d_acc, d.m * N * sizeof(pxb_acceptor_rec));
+    if (e == hipSuccess) e = hipMemsetAsync(d.d_tot, 0, PXB_NCOUNTERS * sizeof(int64_t), d.st);
+    return done(g, hip_rc(e));
   }
 
   int compute(int g) {
     Dev& d = dv[g];
     if (injected("compute", g)) return PXB_E_HIP;
-    if (hipSetDevice(g) != hipSuccess) return PXB_E_HIP;
+    if (hipError_t e = hipSetDevice(g)) return done(g, hip_fail(e));
     pxb_config c = *cfg;
     c.first_instance = cfg->first_instance + d.lo;
     c.n_instances = d.m;
-    if (int r = pxb_run_device(&c, d.d_out, d.d_dig, d.d_acc, d.d_tot, d.st)) return r;
-    if (hipStreamSynchronize(d.st) != hipSuccess) return PXB_E_HIP;
+    if (int r = pxb_run_device(&c, d.d_out, d.d_dig, d.d_acc, d.d_tot, d.st)) return done(g, r);
     const uint64_t N = cfg->n_acceptors;
-    if (out && d.m && hipMemcpy(out + d.lo, d.d_out, d.m * sizeof(pxb_result), hipMemcpyDeviceToHost) != hipSuccess)
-      return PXB_E_HIP;
-    if (log_digest && d.m &&
-        hipMemcpy(log_digest + d.lo * N, d.d_dig, d.m * N * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-      return PXB_E_HIP;
-    if (acc && d.m &&
-        hipMemcpy(acc + d.lo * N, d.d_acc, d.m * N * sizeof(pxb_acceptor_rec), hipMemcpyDeviceToHost) != hipSuccess)
-      return PXB_E_HIP;
-    return PXB_OK;
+    hipError_t e = hipStreamSynchronize(d.st);
+    if (e == hipSuccess && out && d.m) e = hipMemcpy(out + d.lo, d.d_out, d.m * sizeof(pxb_result), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && log_digest && d.m)
+      e = hipMemcpy(log_digest + d.lo * N, d.d_dig, d.m * N * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && acc && d.m)
+      e = hipMemcpy(acc + d.lo * N, d.d_acc, d.m * N * sizeof(pxb_acceptor_rec), hipMemcpyDeviceToHost);
+    return done(g, hip_rc(e));
   }
 
   // the run's one collective, issued for every device in one group
@@ -152,10 +160,10 @@ struct HipShards {
 
   int fetch(int g) {
     Dev& d = dv[g];
-    if (hipSetDevice(g) != hipSuccess || hipStreamSynchronize(d.st) != hipSuccess) return PXB_E_HIP;
-    if (hipMemcpy(d.tot, d.d_tot, PXB_NCOUNTERS * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
-      return PXB_E_HIP;
-    return PXB_OK;
+    hipError_t e = hipSetDevice(g);
+    if (e == hipSuccess) e = hipStreamSynchronize(d.st);
+    if (e == hipSuccess) e = hipMemcpy(d.tot, d.d_tot, PXB_NCOUNTERS * sizeof(int64_t), hipMemcpyDeviceToHost);
+    return done(g, hip_rc(e));
   }
 
   void teardown(int g) {
@@ -205,6 +213,8 @@ int pxb_run_multi(const pxb_config* cfg, int n_devices, pxb_result* out, uint32_
   if (int rc = comms_for(G, b.comms)) return rc;
   const int rc = pxb::run_shards(b, G);
   (void)hipSetDevice(cur);
+  for (int g = G - 1; rc && g >= 0; --g)          // (the calling thread's pxb_last_hip_error: the first device's that has one)
+    if (b.dv[g].hip) pxb::host::set_last_hip_error(b.dv[g].hip);
   if (rc) return rc;
   if (totals) memcpy(totals->c, b.dv[0].tot, PXB_NCOUNTERS * sizeof(int64_t));   // the reduced totals
   return PXB_OK;

@@ -188,14 +188,15 @@ int pxb_query_device(const pxb_result* d_results, uint64_t first_instance, uint6
   const hipStream_t st = (hipStream_t)stream;
   int dev = 0, cus = 0;
   if (int rc = current_device(&dev)) return rc;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) return PXB_E_HIP;
+  if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return hip_fail(e);
+  if (cus < 1) return hip_fail(hipErrorInvalidDevice);
 
   const uint64_t ntiles = (count + WTILE - 1) / WTILE;
   const uint64_t iters = (count + BTILE - 1) / BTILE;
   widen_iter counts(nullptr, Widen{});
   size_t need = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, (uint64_t*)nullptr, (int64_t)ntiles, st) != hipSuccess)
-    return PXB_E_HIP;
+  if (hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, (uint64_t*)nullptr, (int64_t)ntiles, st))
+    return hip_fail(e);
   const size_t cnt_b = pad256(ntiles * sizeof(uint32_t)), off_b = pad256(ntiles * sizeof(uint64_t));
   void* buf = nullptr;
   if (int rc = pxw::scratch(dev, 256 + cnt_b + off_b + need, st, &buf)) return rc;

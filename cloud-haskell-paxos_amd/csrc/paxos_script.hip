@@ -192,12 +192,10 @@ static ScrParams params(const pxb_config* cfg, const uint8_t* d_rows, uint64_t c
   return k;
 }
 
-static size_t scan_bytes(uint64_t count, hipStream_t st) {
-  size_t need = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, kept_iter(nullptr, Kept{0u}), (uint64_t*)nullptr,
-                                       (int64_t)(count + 1), st) != hipSuccess)
-    return (size_t)-1;
-  return need;
+static hipError_t scan_bytes(uint64_t count, hipStream_t st, size_t* need) {
+  *need = 0;
+  return hipcub::DeviceScan::ExclusiveSum(nullptr, *need, kept_iter(nullptr, Kept{0u}), (uint64_t*)nullptr,
+                                          (int64_t)(count + 1), st);
 }
 
 }  // namespace pxsc
@@ -270,8 +268,8 @@ int pxb_trace_scripted_device(const pxb_config* cfg, const uint8_t* d_rows, uint
     const hipError_t e = hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st);
     return (e == hipSuccess) ? PXB_OK : hip_fail(e);
   }
-  size_t need = scan_bytes(count, st);
-  if (need == (size_t)-1) return PXB_E_HIP;
+  size_t need = 0;
+  if (hipError_t e = scan_bytes(count, st, &need)) return hip_fail(e);
   const size_t cnt_b = pad256((count + 1) * sizeof(uint32_t));
   void* buf = nullptr;
   if (int rc = pxw::scratch(dev, cnt_b + need, st, &buf)) return rc;
@@ -307,28 +305,22 @@ int pxb_trace_scripted_device(const pxb_config* cfg, const uint8_t* d_rows, uint
   return (e == hipSuccess) ? PXB_OK : hip_fail(e);
 }
 
-// ---- HOST-buffer forms: device copies of the buffers around the device forms ----
+// ---- HOST-buffer forms: device copies of the buffers (host_stage.h) around the device forms ----
 int pxb_schedule_extract(const pxb_config* cfg, const uint64_t* ids, uint64_t count, uint32_t depth, uint8_t* rows) {
   using namespace pxsc;
   if (int rc = validate_cfg(cfg, ids, count, depth)) return rc;
   if (count && !rows) return PXB_E_INVAL;
   if (device_count() == 0) return PXB_E_NODEV;
   if (count == 0) return PXB_OK;
-  const size_t rows_b = (size_t)(count * script_stride(cfg->n_proposers, cfg->n_acceptors, depth));
-  const size_t ids_b = pad256(count * sizeof(uint64_t));
-  char* buf = nullptr;
-  hipError_t e = hipMalloc(&buf, ids_b + rows_b);
-  if (e != hipSuccess) return hip_fail(e);
-  int rc = PXB_OK;
-  do {
-    if ((e = hipMemcpy(buf, ids, count * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
-    rc = pxb_schedule_extract_device(cfg, reinterpret_cast<uint64_t*>(buf), count, depth,
-                                     reinterpret_cast<uint8_t*>(buf + ids_b), nullptr);
-    if (rc) break;
-    e = hipMemcpy(rows, buf + ids_b, rows_b, hipMemcpyDeviceToHost);
-  } while (0);
-  (void)hipFree(buf);
-  return rc ? rc : (e == hipSuccess) ? PXB_OK : hip_fail(e);
+  pxb::StagePlan plan;
+  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), count);
+  const pxb::StageRegion r_rows = plan.add(script_stride(cfg->n_proposers, cfg->n_acceptors, depth), count);
+  Staging S(plan);
+  S.up(r_ids, ids, count);
+  if (S.ok())
+    S.note(pxb_schedule_extract_device(cfg, S.ptr<uint64_t>(r_ids), count, depth, S.ptr<uint8_t>(r_rows), nullptr));
+  S.down(r_rows, rows, count);
+  return S.finish();
 }
 
 int pxb_run_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth, pxb_result* out,
@@ -337,42 +329,25 @@ int pxb_run_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t count,
   if (int rc = validate_cfg(cfg, rows, count, depth)) return rc;
   if (device_count() == 0) return PXB_E_NODEV;
   if (count == 0) return PXB_OK;
-  const uint32_t P = cfg->n_proposers, N = cfg->n_acceptors;
-  const size_t rows_b = pad256((size_t)(count * script_stride(P, N, depth)));
-  const size_t out_b = pad256(count * sizeof(pxb_result)), dig_b = pad256(count * N * sizeof(uint32_t));
-  const size_t acc_b = pad256(count * N * sizeof(pxb_acceptor_rec)), st_b = pad256(count * sizeof(uint32_t));
-  const size_t sent_b = pad256(count * 2u * P * N * sizeof(uint16_t));
-  char* buf = nullptr;                            // rows | results | digests | records | status | sent
-  hipError_t e = hipMalloc(&buf, rows_b + out_b + dig_b + acc_b + st_b + sent_b);
-  if (e != hipSuccess) return hip_fail(e);
-  char* const d_out = buf + rows_b;
-  char* const d_dig = d_out + out_b;
-  char* const d_acc = d_dig + dig_b;
-  char* const d_st = d_acc + acc_b;
-  char* const d_sent = d_st + st_b;
-  int rc = PXB_OK;
-  do {
-    if ((e = hipMemcpy(buf, rows, (size_t)(count * script_stride(P, N, depth)), hipMemcpyHostToDevice)) != hipSuccess)
-      break;
-    rc = pxb_run_scripted_device(cfg, reinterpret_cast<uint8_t*>(buf), count, depth,
-                                 out ? reinterpret_cast<pxb_result*>(d_out) : nullptr,
-                                 log_digest ? reinterpret_cast<uint32_t*>(d_dig) : nullptr,
-                                 acc ? reinterpret_cast<pxb_acceptor_rec*>(d_acc) : nullptr,
-                                 status ? reinterpret_cast<uint32_t*>(d_st) : nullptr,
-                                 sent ? reinterpret_cast<uint16_t*>(d_sent) : nullptr, nullptr);
-    if (rc) break;
-    if (out && (e = hipMemcpy(out, d_out, count * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (log_digest && (e = hipMemcpy(log_digest, d_dig, count * N * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-    if (acc && (e = hipMemcpy(acc, d_acc, count * N * sizeof(pxb_acceptor_rec), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-    if (status && (e = hipMemcpy(status, d_st, count * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (sent && (e = hipMemcpy(sent, d_sent, count * 2u * P * N * sizeof(uint16_t), hipMemcpyDeviceToHost)) != hipSuccess)
-      break;
-    e = hipDeviceSynchronize();
-  } while (0);
-  (void)hipFree(buf);
-  return rc ? rc : (e == hipSuccess) ? PXB_OK : hip_fail(e);
+  const uint64_t P = cfg->n_proposers, N = cfg->n_acceptors;
+  pxb::StagePlan plan;                            // rows | results | digests | records | status | sent
+  const pxb::StageRegion r_rows = plan.add(script_stride(cfg->n_proposers, cfg->n_acceptors, depth), count);
+  const pxb::StageRegion r_out = plan.add(sizeof(pxb_result), count), r_dig = plan.add(N * sizeof(uint32_t), count);
+  const pxb::StageRegion r_acc = plan.add(N * sizeof(pxb_acceptor_rec), count), r_st = plan.add(sizeof(uint32_t), count);
+  const pxb::StageRegion r_sent = plan.add(2u * P * N * sizeof(uint16_t), count);
+  Staging S(plan);
+  S.up(r_rows, rows, count);
+  // (an output that was not asked for: null, and the kernel does not store it)
+  if (S.ok())
+    S.note(pxb_run_scripted_device(cfg, S.ptr<uint8_t>(r_rows), count, depth, S.ptr<pxb_result>(r_out, out),
+                                   S.ptr<uint32_t>(r_dig, log_digest), S.ptr<pxb_acceptor_rec>(r_acc, acc),
+                                   S.ptr<uint32_t>(r_st, status), S.ptr<uint16_t>(r_sent, sent), nullptr));
+  S.down(r_out, out, count);
+  S.down(r_dig, log_digest, count);
+  S.down(r_acc, acc, count);
+  S.down(r_st, status, count);
+  S.down(r_sent, sent, count);
+  return S.finish();
 }
 
 int pxb_trace_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
@@ -382,44 +357,14 @@ int pxb_trace_scripted(const pxb_config* cfg, const uint8_t* rows, uint64_t coun
   scr_ptr fn = nullptr;
   if (int rc = validate_trace(cfg, rows, count, depth, sel, records, capacity, offsets, &fn)) return rc;
   if (device_count() == 0) return PXB_E_NODEV;
-  if (count == 0) {
-    offsets[0] = 0;
-    if (n_records) *n_records = 0;
-    return PXB_OK;
-  }
-  const size_t rows_n = (size_t)(count * script_stride(cfg->n_proposers, cfg->n_acceptors, depth));
-  const size_t rows_b = pad256(rows_n), off_b = pad256((count + 1) * sizeof(uint64_t));
-  const size_t st_b = pad256(count * sizeof(uint32_t)), res_b = pad256(count * sizeof(pxb_result));
-  char* buf = nullptr;                            // rows | offsets | status | results
-  pxb_trace_step* d_rec = nullptr;
-  hipError_t e = hipMalloc(&buf, rows_b + off_b + st_b + res_b);
-  if (e != hipSuccess) return hip_fail(e);
-  uint8_t* const d_rows = reinterpret_cast<uint8_t*>(buf);
-  uint64_t* const d_off = reinterpret_cast<uint64_t*>(buf + rows_b);
-  uint32_t* const d_st = reinterpret_cast<uint32_t*>(buf + rows_b + off_b);
-  pxb_result* const d_res = reinterpret_cast<pxb_result*>(buf + rows_b + off_b + st_b);
-  int rc = PXB_OK;
-  do {
-    if ((e = hipMemcpy(d_rows, rows, rows_n, hipMemcpyHostToDevice)) != hipSuccess) break;
-    // the sizing call, then (records to write) the call again with the records' buffer
-    rc = pxb_trace_scripted_device(cfg, d_rows, count, depth, sel, nullptr, 0, d_off, d_st, d_res, nullptr);
-    if (rc) break;
-    if ((e = hipMemcpy(offsets, d_off, (count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    const uint64_t total = offsets[count], m = total < capacity ? total : capacity;
-    if (m) {
-      if ((e = hipMalloc(&d_rec, m * sizeof(pxb_trace_step))) != hipSuccess) break;
-      rc = pxb_trace_scripted_device(cfg, d_rows, count, depth, sel, d_rec, m, d_off, d_st, d_res, nullptr);
-      if (rc) break;
-      if ((e = hipMemcpy(records, d_rec, m * sizeof(pxb_trace_step), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    }
-    if (status && (e = hipMemcpy(status, d_st, count * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (results && (e = hipMemcpy(results, d_res, count * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (n_records) *n_records = total;
-    e = hipDeviceSynchronize();
-  } while (0);
-  if (d_rec) (void)hipFree(d_rec);
-  (void)hipFree(buf);
-  return rc ? rc : (e == hipSuccess) ? PXB_OK : hip_fail(e);
+  // (both calls get the status and results buffers, whatever the caller asked for)
+  const auto call = [&](Staging&, const TraceBufs& d, pxb_trace_step* d_rec = nullptr, uint64_t m = 0) {
+    return pxb_trace_scripted_device(cfg, static_cast<uint8_t*>(d.in), count, depth, sel, d_rec, m, d.off, d.st, d.res,
+                                     nullptr);
+  };
+  pxb::StagePlan plan;                            // rows | offsets | status | results
+  return trace_two_call(plan, rows, script_stride(cfg->n_proposers, cfg->n_acceptors, depth), count, records, capacity,
+                        offsets, status, results, n_records, call, call);
 }
 
 }  // extern "C"

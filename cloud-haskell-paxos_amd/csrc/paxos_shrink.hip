@@ -345,9 +345,9 @@ int pxb_shrink_batch_device(const pxb_config* cfg, uint8_t* d_rows, uint64_t cou
   k.tstride = shrink_tstride(k.d);
 
   size_t scan_b = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
-                                       (int64_t)(count + 1), st) != hipSuccess)
-    return PXB_E_HIP;
+  if (hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
+                                                      (int64_t)(count + 1), st))
+    return hip_fail(e);
   // the call's scratch: work rows | tables | sent | counts | offsets | state | launches | faults | results | scan
   // (the rows are shrunk in a copy and written back at the end: a failed call writes nothing)
   const size_t rows_b = pad256((size_t)(count * k.stride)), tab_b = pad256((size_t)(count * k.tstride * 2u));
@@ -453,48 +453,35 @@ int pxb_shrink_batch(const pxb_config* cfg, const uint64_t* ids, uint8_t* rows, 
   if (int rc = validate(cfg, rows, count, depth, flag_mask, max_launches, &fn)) return rc;
   if (device_count() == 0) return PXB_E_NODEV;
   if (count == 0) return PXB_OK;
-  const uint32_t NL = 2u * cfg->n_proposers * cfg->n_acceptors;
-  const size_t rows_n = (size_t)(count * script_stride(cfg->n_proposers, cfg->n_acceptors, depth));
-  const size_t rows_b = pad256(rows_n), ids_b = pad256(count * 8u), w_b = pad256(count * 4u);
-  const size_t sent_b = pad256(count * NL * 2u), res_b = pad256(count * 16u), sig_b = pad256(count * 8u);
-  char* buf = nullptr;                            // rows | ids | status | faults | launches | sent | results | signature
-  hipError_t e = hipMalloc(&buf, rows_b + ids_b + 3u * w_b + sent_b + res_b + sig_b);
-  if (e != hipSuccess) return hip_fail(e);
-  uint8_t* const d_rows = reinterpret_cast<uint8_t*>(buf);
-  uint64_t* const d_ids = reinterpret_cast<uint64_t*>(buf + rows_b);
-  char* const d_st = buf + rows_b + ids_b;
-  char* const d_nf = d_st + w_b;
-  char* const d_la = d_nf + w_b;
-  char* const d_sent = d_la + w_b;
-  char* const d_res = d_sent + sent_b;
-  char* const d_sig = d_res + res_b;
-  int rc = PXB_OK;
-  do {
-    if (ids) {
-      if ((e = hipMemcpy(d_ids, ids, count * 8u, hipMemcpyHostToDevice)) != hipSuccess) break;
-      if ((rc = pxb_schedule_extract_device(cfg, d_ids, count, depth, d_rows, nullptr))) break;
-    } else if ((e = hipMemcpy(d_rows, rows, rows_n, hipMemcpyHostToDevice)) != hipSuccess) {
-      break;
-    }
-    rc = pxb_shrink_batch_device(cfg, d_rows, count, depth, flag_mask, max_launches,
-                                 status ? reinterpret_cast<uint32_t*>(d_st) : nullptr,
-                                 n_faults ? reinterpret_cast<uint32_t*>(d_nf) : nullptr,
-                                 launches ? reinterpret_cast<uint32_t*>(d_la) : nullptr,
-                                 sent ? reinterpret_cast<uint16_t*>(d_sent) : nullptr,
-                                 results ? reinterpret_cast<pxb_result*>(d_res) : nullptr,
-                                 signature ? reinterpret_cast<uint64_t*>(d_sig) : nullptr, nullptr);
-    if (rc) break;
-    if ((e = hipMemcpy(rows, d_rows, rows_n, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (status && (e = hipMemcpy(status, d_st, count * 4u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (n_faults && (e = hipMemcpy(n_faults, d_nf, count * 4u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (launches && (e = hipMemcpy(launches, d_la, count * 4u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (sent && (e = hipMemcpy(sent, d_sent, count * NL * 2u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (results && (e = hipMemcpy(results, d_res, count * 16u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (signature && (e = hipMemcpy(signature, d_sig, count * 8u, hipMemcpyDeviceToHost)) != hipSuccess) break;
-    e = hipDeviceSynchronize();
-  } while (0);
-  (void)hipFree(buf);
-  return rc ? rc : (e == hipSuccess) ? PXB_OK : hip_fail(e);
+  const uint64_t NL = 2u * cfg->n_proposers * cfg->n_acceptors;
+  pxb::StagePlan plan;                            // rows | ids | status | faults | launches | sent | results | signature
+  const pxb::StageRegion r_rows = plan.add(script_stride(cfg->n_proposers, cfg->n_acceptors, depth), count);
+  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), count);
+  const pxb::StageRegion r_st = plan.add(sizeof(uint32_t), count), r_nf = plan.add(sizeof(uint32_t), count);
+  const pxb::StageRegion r_la = plan.add(sizeof(uint32_t), count), r_sent = plan.add(NL * sizeof(uint16_t), count);
+  const pxb::StageRegion r_res = plan.add(sizeof(pxb_result), count), r_sig = plan.add(sizeof(uint64_t), count);
+  Staging S(plan);
+  uint8_t* const d_rows = S.ptr<uint8_t>(r_rows);
+  if (ids) {
+    S.up(r_ids, ids, count);
+    if (S.ok()) S.note(pxb_schedule_extract_device(cfg, S.ptr<uint64_t>(r_ids), count, depth, d_rows, nullptr));
+  } else {
+    S.up(r_rows, rows, count);
+  }
+  // (an output that was not asked for: null, and the finish kernel does not store it)
+  if (S.ok())
+    S.note(pxb_shrink_batch_device(cfg, d_rows, count, depth, flag_mask, max_launches, S.ptr<uint32_t>(r_st, status),
+                                   S.ptr<uint32_t>(r_nf, n_faults), S.ptr<uint32_t>(r_la, launches),
+                                   S.ptr<uint16_t>(r_sent, sent), S.ptr<pxb_result>(r_res, results),
+                                   S.ptr<uint64_t>(r_sig, signature), nullptr));
+  S.down(r_rows, rows, count);
+  S.down(r_st, status, count);
+  S.down(r_nf, n_faults, count);
+  S.down(r_la, launches, count);
+  S.down(r_sent, sent, count);
+  S.down(r_res, results, count);
+  S.down(r_sig, signature, count);
+  return S.finish();
 }
 
 }  // extern "C"

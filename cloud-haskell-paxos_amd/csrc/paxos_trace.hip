@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/paxos_batch.h"
+#include "host_stage.h"
 #include "lane_shapes.h"
 #include "paxos_ev_kernel.h"
 #include "paxos_trace_core.h"   // trace_record, trace_config_ok
@@ -104,32 +105,22 @@ extern "C" int pxb_trace_instance(const pxb_config* cfg, uint64_t instance, pxb_
   if (!fn) return PXB_E_INVAL;
   EvParams p = make_params(cfg);
   p.first_instance = instance;
-  pxb_trace_step* d_out = nullptr;
-  uint32_t* d_st = nullptr;
-  uint4* d_res = nullptr;
-  int rc = PXB_OK;
-  hipError_t e = hipSuccess;
+  pxb::StagePlan plan;                            // records | status words | result: one block
+  const pxb::StageRegion r_out = plan.add(sizeof(pxb_trace_step), max_records);
+  const pxb::StageRegion r_st = plan.add(sizeof(uint32_t), 2), r_res = plan.add(sizeof(uint4), 1);
+  pxb::host::Staging S(plan);
   uint32_t st[2] = {0, 0};
-  do {
-    if ((e = hipMalloc(&d_out, (size_t)max_records * sizeof(pxb_trace_step))) != hipSuccess) break;
-    if ((e = hipMalloc(&d_st, 2 * sizeof(uint32_t))) != hipSuccess) break;
-    if ((e = hipMalloc(&d_res, sizeof(uint4))) != hipSuccess) break;
-    if ((e = hipMemset(d_st, 0, 2 * sizeof(uint32_t))) != hipSuccess) break;
-    hipLaunchKernelGGL(fn, dim3(1), dim3(64), 0, 0, p, 0u, d_out, max_records, d_st, d_res);
-    if ((e = hipGetLastError()) != hipSuccess) break;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-    if ((e = hipMemcpy(st, d_st, sizeof(st), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (st[1]) {
-      rc = PXB_E_INVAL;
-      break;
-    }
-    if ((e = hipMemcpy(out, d_out, (size_t)st[0] * sizeof(pxb_trace_step), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (result && (e = hipMemcpy(result, d_res, sizeof(uint4), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    *n_records = st[0];
-  } while (0);
-  if (d_out) (void)hipFree(d_out);
-  if (d_st) (void)hipFree(d_st);
-  if (d_res) (void)hipFree(d_res);
-  if (e != hipSuccess) return (e == hipErrorOutOfMemory) ? PXB_E_OOM : PXB_E_HIP;
-  return rc;
+  S.zero(r_st);
+  if (S.ok()) {
+    hipLaunchKernelGGL(fn, dim3(1), dim3(64), 0, 0, p, 0u, S.ptr<pxb_trace_step>(r_out), max_records,
+                       S.ptr<uint32_t>(r_st), S.ptr<uint4>(r_res));
+    S.note(hipGetLastError());
+  }
+  S.sync();
+  S.down(r_st, st, 2);
+  if (S.ok() && st[1]) S.note(PXB_E_INVAL);
+  S.down(r_out, out, st[0]);
+  S.down(r_res, result, 1);
+  if (S.ok()) *n_records = st[0];
+  return S.finish();
 }

@@ -113,12 +113,10 @@ int validate(const pxb_config* cfg, const void* ids, uint64_t count, const pxb_t
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 
-size_t scan_bytes(uint64_t count, hipStream_t st) {
-  size_t need = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, kept_iter(nullptr, Kept{0u}), (uint64_t*)nullptr,
-                                       (int64_t)(count + 1), st) != hipSuccess)
-    return (size_t)-1;
-  return need;
+hipError_t scan_bytes(uint64_t count, hipStream_t st, size_t* need) {
+  *need = 0;
+  return hipcub::DeviceScan::ExclusiveSum(nullptr, *need, kept_iter(nullptr, Kept{0u}), (uint64_t*)nullptr,
+                                          (int64_t)(count + 1), st);
 }
 
 // count pass + scan (phase 1), write pass (phase 2) over cnt (count + 1 words) and the scan's tmp
@@ -179,8 +177,8 @@ int pxb_trace_batch_device(const pxb_config* cfg, const uint64_t* d_ids, uint64_
     const hipError_t e = hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st);
     return (e == hipSuccess) ? PXB_OK : hip_fail(e);
   }
-  const size_t need = scan_bytes(count, st);
-  if (need == (size_t)-1) return PXB_E_HIP;
+  size_t need = 0;
+  if (hipError_t e = scan_bytes(count, st, &need)) return hip_fail(e);
   const size_t cnt_b = pad256((count + 1) * sizeof(uint32_t));
   void* buf = nullptr;
   if (int rc = pxw::scratch(dev, cnt_b + need, st, &buf)) return rc;
@@ -198,46 +196,21 @@ int pxb_trace_batch(const pxb_config* cfg, const uint64_t* ids, uint64_t count, 
   trb_ptr fn = nullptr;
   if (int rc = validate(cfg, ids, count, sel, records, capacity, offsets, &fn)) return rc;
   if (device_count() == 0) return PXB_E_NODEV;
-  if (count == 0) {
-    offsets[0] = 0;
-    if (n_records) *n_records = 0;
-    return PXB_OK;
-  }
-  const size_t need = scan_bytes(count, 0);
-  if (need == (size_t)-1) return PXB_E_HIP;
-  const size_t ids_b = pad256(count * sizeof(uint64_t)), off_b = pad256((count + 1) * sizeof(uint64_t));
-  const size_t cnt_b = pad256((count + 1) * sizeof(uint32_t)), st_b = pad256(count * sizeof(uint32_t));
-  const size_t res_b = pad256(count * sizeof(pxb_result));
-  char* buf = nullptr;                            // ids | offsets | counts | status | results | the scan's
-  pxb_trace_step* d_rec = nullptr;
-  hipError_t e = hipSuccess;
-  do {
-    if ((e = hipMalloc(&buf, ids_b + off_b + cnt_b + st_b + res_b + need)) != hipSuccess) break;
-    uint64_t* d_ids = reinterpret_cast<uint64_t*>(buf);
-    uint64_t* d_off = reinterpret_cast<uint64_t*>(buf + ids_b);
-    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(buf + ids_b + off_b);
-    uint32_t* d_st = reinterpret_cast<uint32_t*>(buf + ids_b + off_b + cnt_b);
-    pxb_result* d_res = reinterpret_cast<pxb_result*>(buf + ids_b + off_b + cnt_b + st_b);
-    void* tmp = buf + ids_b + off_b + cnt_b + st_b + res_b;
-    if ((e = hipMemcpy(d_ids, ids, count * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
-    if ((e = launch(fn, cfg, d_ids, count, sel, nullptr, 0, d_off, status ? d_st : nullptr, results ? d_res : nullptr,
-                    0, d_cnt, tmp, need, 1)) != hipSuccess)
-      break;
-    if ((e = hipMemcpy(offsets, d_off, (count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    const uint64_t total = offsets[count], m = total < capacity ? total : capacity;
-    if (m) {
-      if ((e = hipMalloc(&d_rec, m * sizeof(pxb_trace_step))) != hipSuccess) break;
-      if ((e = launch(fn, cfg, d_ids, count, sel, d_rec, m, d_off, nullptr, nullptr, 0, d_cnt, tmp, need, 2)) != hipSuccess)
-        break;
-      if ((e = hipMemcpy(records, d_rec, m * sizeof(pxb_trace_step), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    }
-    if (status && (e = hipMemcpy(status, d_st, count * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (results && (e = hipMemcpy(results, d_res, count * sizeof(pxb_result), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (n_records) *n_records = total;
-  } while (0);
-  if (d_rec) (void)hipFree(d_rec);
-  if (buf) (void)hipFree(buf);
-  return (e == hipSuccess) ? PXB_OK : hip_fail(e);
+  size_t need = 0;
+  if (count)
+    if (hipError_t e = scan_bytes(count, 0, &need)) return hip_fail(e);
+  pxb::StagePlan plan;                            // counts | the scan's | ids | offsets | status | results
+  const pxb::StageRegion r_cnt = plan.add(sizeof(uint32_t), count + 1), r_tmp = plan.add(1, need);
+  // the count pass and the scan once, then the write pass alone over their counts and offsets: not the
+  // device form twice (the count pass stores no status or results that were not asked for)
+  const auto pass = [&](Staging& S, const TraceBufs& d, pxb_trace_step* d_rec, uint64_t m, bool first) {
+    return launch(fn, cfg, static_cast<uint64_t*>(d.in), count, sel, d_rec, m, d.off, first && status ? d.st : nullptr,
+                  first && results ? d.res : nullptr, 0, S.ptr<uint32_t>(r_cnt), S.ptr<char>(r_tmp), need, first ? 1 : 2);
+  };
+  return trace_two_call(
+      plan, ids, sizeof(uint64_t), count, records, capacity, offsets, status, results, n_records,
+      [&](Staging& S, const TraceBufs& d) { return pass(S, d, nullptr, 0, true); },
+      [&](Staging& S, const TraceBufs& d, pxb_trace_step* d_rec, uint64_t m) { return pass(S, d, d_rec, m, false); });
 }
 
 }  // extern "C"

@@ -397,7 +397,7 @@ void pxb_wire_release(void) {
 int pxb_wire_size(const pxb_msg* d_msgs, uint64_t count, uint32_t type, uint64_t* d_offsets, void* stream) {
   if (type > PXB_WIRE_RESPONSE || !d_offsets || (count && !d_msgs) || count > (1ull << 40)) return PXB_E_INVAL;
   const hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st) != hipSuccess) return PXB_E_HIP;
+  if (hipError_t e = hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st)) return hip_fail(e);
   if (count == 0) return PXB_OK;
   int dev = 0;
   if (int rc = current_device(&dev)) return rc;
@@ -405,8 +405,8 @@ int pxb_wire_size(const pxb_msg* d_msgs, uint64_t count, uint32_t type, uint64_t
   // scan reads the messages
   hipcub::TransformInputIterator<uint64_t, SizeOp, const pxb_msg*> sizes(d_msgs, SizeOp{type});
   size_t need = 0;
-  if (hipcub::DeviceScan::InclusiveSum(nullptr, need, sizes, d_offsets + 1, (int64_t)count, st) != hipSuccess)
-    return PXB_E_HIP;
+  if (hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, need, sizes, d_offsets + 1, (int64_t)count, st))
+    return hip_fail(e);
   void* tmp = nullptr;
   if (int rc = scratch(dev, need, st, &tmp)) return rc;
   hipError_t e = hipcub::DeviceScan::InclusiveSum(tmp, need, sizes, d_offsets + 1, (int64_t)count, st);
@@ -422,22 +422,22 @@ int pxb_wire_encode(const pxb_msg* d_msgs, uint64_t count, uint32_t type, const 
   if (!d_msgs || !d_offsets || !d_bytes) return PXB_E_INVAL;
   hipLaunchKernelGGL(encode_kernel<false>, dim3(tiles_of(count, ETILE)), dim3(ETILE), 0, (hipStream_t)stream, d_msgs,
                      count, type, const_cast<uint64_t*>(d_offsets), nullptr, d_bytes);
-  return (hipGetLastError() == hipSuccess) ? PXB_OK : PXB_E_HIP;
+  return hip_rc(hipGetLastError());
 }
 
 int pxb_wire_encode_all(const pxb_msg* d_msgs, uint64_t count, uint32_t type, uint64_t* d_offsets,
                         uint8_t* d_bytes, void* stream) {
   if (type > PXB_WIRE_RESPONSE || !d_offsets || count > (1ull << 40)) return PXB_E_INVAL;
   const hipStream_t st = (hipStream_t)stream;
-  if (count == 0) return (hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st) == hipSuccess) ? PXB_OK : PXB_E_HIP;
+  if (count == 0) return hip_rc(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), st));
   if (!d_msgs || !d_bytes) return PXB_E_INVAL;
   int dev = 0;
   if (int rc = current_device(&dev)) return rc;
   const uint64_t tiles = tiles_of(count, ETILE);
   size_t need = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, need, (uint64_t*)nullptr, (uint64_t*)nullptr, (int64_t)tiles, st) !=
-      hipSuccess)
-    return PXB_E_HIP;
+  if (hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                      (int64_t)tiles, st))
+    return hip_fail(e);
   const size_t arr = pad256(tiles * sizeof(uint64_t));
   void* buf = nullptr;
   if (int rc = scratch(dev, 2 * arr + need, st, &buf)) return rc;
@@ -465,7 +465,7 @@ int pxb_wire_decode(const uint8_t* d_bytes, uint64_t n_bytes, const uint64_t* d_
   if (!d_offsets || !d_msgs || (n_bytes && !d_bytes)) return PXB_E_INVAL;
   hipLaunchKernelGGL(decode_kernel, dim3(tiles_of(count, DTILE)), dim3(DTILE), 0, (hipStream_t)stream, d_bytes, n_bytes,
                      d_offsets, count, type, d_msgs, d_status);
-  return (hipGetLastError() == hipSuccess) ? PXB_OK : PXB_E_HIP;
+  return hip_rc(hipGetLastError());
 }
 
 int pxb_wire_encode_host(const pxb_msg* msgs, uint64_t count, uint32_t type, uint8_t* out, uint64_t* offsets,
@@ -473,27 +473,18 @@ int pxb_wire_encode_host(const pxb_msg* msgs, uint64_t count, uint32_t type, uin
   if (type > PXB_WIRE_RESPONSE || !offsets || !nbytes || (count && (!msgs || !out))) return PXB_E_INVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return PXB_E_NODEV;
-  pxb_msg* d_m = nullptr;
-  uint64_t* d_o = nullptr;
-  uint8_t* d_b = nullptr;
-  hipError_t e = hipSuccess;
-  int rc = PXB_OK;
-  do {
-    if ((e = hipMalloc(&d_o, (count + 1) * sizeof(uint64_t))) != hipSuccess) break;
-    if (count && (e = hipMalloc(&d_m, count * sizeof(pxb_msg))) != hipSuccess) break;
-    if (count && (e = hipMemcpy(d_m, msgs, count * sizeof(pxb_msg), hipMemcpyHostToDevice)) != hipSuccess) break;
-    if ((rc = pxb_wire_size(d_m, count, type, d_o, nullptr)) != PXB_OK) break;
-    if ((e = hipMemcpy(offsets, d_o, (count + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    *nbytes = offsets[count];
-    if (count && (e = hipMalloc(&d_b, *nbytes ? *nbytes : 1)) != hipSuccess) break;
-    if ((rc = pxb_wire_encode(d_m, count, type, d_o, d_b, nullptr)) != PXB_OK) break;
-    if (*nbytes && (e = hipMemcpy(out, d_b, *nbytes, hipMemcpyDeviceToHost)) != hipSuccess) break;
-  } while (0);
-  if (d_m) (void)hipFree(d_m);
-  if (d_o) (void)hipFree(d_o);
-  if (d_b) (void)hipFree(d_b);
-  if (e != hipSuccess) return hip_fail(e);
-  return rc;
+  pxb::StagePlan plan;                            // offsets | messages; the bytes come late, sized by the offsets
+  const pxb::StageRegion r_o = plan.add(sizeof(uint64_t), count + 1), r_m = plan.add(sizeof(pxb_msg), count);
+  Staging S(plan);
+  S.up(r_m, msgs, count);
+  if (S.ok()) S.note(pxb_wire_size(S.ptr<pxb_msg>(r_m), count, type, S.ptr<uint64_t>(r_o), nullptr));
+  S.down(r_o, offsets, count + 1);
+  if (!S.ok()) return S.finish();
+  *nbytes = offsets[count];
+  const pxb::StageRegion r_b = count ? S.late(1, *nbytes ? *nbytes : 1) : pxb::StageRegion{};
+  if (S.ok()) S.note(pxb_wire_encode(S.ptr<pxb_msg>(r_m), count, type, S.ptr<uint64_t>(r_o), S.ptr<uint8_t>(r_b), nullptr));
+  S.down(r_b, out, *nbytes);
+  return S.finish();
 }
 
 int pxb_wire_decode_host(const uint8_t* in, uint64_t n_bytes, const uint64_t* offsets, uint64_t count, uint32_t type,
@@ -505,29 +496,18 @@ int pxb_wire_decode_host(const uint8_t* in, uint64_t n_bytes, const uint64_t* of
   uint64_t nb = 0;                                       // bytes the offsets reach inside the buffer
   for (uint64_t k = 0; k <= count; ++k) nb = (offsets[k] > nb) ? offsets[k] : nb;
   nb = (nb < n_bytes) ? nb : n_bytes;
-  pxb_msg* d_m = nullptr;
-  uint64_t* d_o = nullptr;
-  uint8_t* d_b = nullptr;
-  uint32_t* d_s = nullptr;
-  hipError_t e = hipSuccess;
-  int rc = PXB_OK;
-  do {
-    if ((e = hipMalloc(&d_o, (count + 1) * sizeof(uint64_t))) != hipSuccess) break;
-    if ((e = hipMalloc(&d_m, count * sizeof(pxb_msg))) != hipSuccess) break;
-    if ((e = hipMalloc(&d_b, nb ? nb : 1)) != hipSuccess) break;
-    if (status && (e = hipMalloc(&d_s, count * sizeof(uint32_t))) != hipSuccess) break;
-    if ((e = hipMemcpy(d_o, offsets, (count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess) break;
-    if (nb && (e = hipMemcpy(d_b, in, nb, hipMemcpyHostToDevice)) != hipSuccess) break;
-    if ((rc = pxb_wire_decode(d_b, nb, d_o, count, type, d_m, d_s, nullptr)) != PXB_OK) break;
-    if ((e = hipMemcpy(msgs, d_m, count * sizeof(pxb_msg), hipMemcpyDeviceToHost)) != hipSuccess) break;
-    if (status && (e = hipMemcpy(status, d_s, count * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) break;
-  } while (0);
-  if (d_m) (void)hipFree(d_m);
-  if (d_o) (void)hipFree(d_o);
-  if (d_b) (void)hipFree(d_b);
-  if (d_s) (void)hipFree(d_s);
-  if (e != hipSuccess) return hip_fail(e);
-  return rc;
+  pxb::StagePlan plan;                            // offsets | messages | bytes (never empty) | status
+  const pxb::StageRegion r_o = plan.add(sizeof(uint64_t), count + 1), r_m = plan.add(sizeof(pxb_msg), count);
+  const pxb::StageRegion r_b = plan.add(1, nb ? nb : 1), r_s = plan.add(sizeof(uint32_t), status ? count : 0);
+  Staging S(plan);
+  S.up(r_o, offsets, count + 1);
+  S.up(r_b, in, nb);
+  if (S.ok())
+    S.note(pxb_wire_decode(S.ptr<uint8_t>(r_b), nb, S.ptr<uint64_t>(r_o), count, type, S.ptr<pxb_msg>(r_m),
+                           S.ptr<uint32_t>(r_s), nullptr));
+  S.down(r_m, msgs, count);
+  S.down(r_s, status, count);
+  return S.finish();
 }
 
 }  // extern "C"
