@@ -51,6 +51,12 @@ module PaxosBatch
   , Message (..)
   , TraceEvent (..)
   , traceEvents
+    -- * Handler-path coverage (docs/SEMANTICS.md §14)
+  , CoverSummary (..)
+  , CoverQuery (..)
+  , coverClasses
+  , cover
+  , coverRange
   , ShrinkStatus (..)
   , Shrunk (..)
   , shrinkBatch
@@ -194,6 +200,14 @@ foreign import ccall safe "pxb_trace_scripted"
 foreign import ccall safe "pxb_trace_events"
   c_pxb_trace_events :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Word64
                      -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word64 -> IO CInt
+
+foreign import ccall safe "pxb_cover"
+  c_pxb_cover :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word32 -> Ptr Word32
+              -> Ptr Word64 -> IO CInt
+
+foreign import ccall safe "pxb_cover_range"
+  c_pxb_cover_range :: Ptr BatchConfig -> Word64 -> Word64 -> Word64 -> Ptr Word32 -> Ptr Word64 -> Ptr Word32
+                    -> Word64 -> Ptr Word64 -> IO CInt
 
 foreign import ccall safe "pxb_shrink_batch"
   c_pxb_shrink_batch :: Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Word32
@@ -610,6 +624,97 @@ traceEvents cfg rows n depth sel = do
                                   traceEvent <$> peekArray nw (advancePtr pb (nw * k))
                                 [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
                                 pure (Just (evs, decode v t r f)))
+
+-- | PXB_COVER_CLASSES: the classes of a coverage mask, bits 0 .. 28.
+coverClasses :: Int
+coverClasses = 29
+
+-- | pxb_cover_summary (680 bytes: 4 + 32 + 32 words of 64 bits, 32 + 2 words of
+-- 32 bits, no padding) as lists of 'coverClasses' entries, indexed by bit.
+-- 'csWitness': the row index ('cover') or instance id ('coverRange') of the OK
+-- row with the class that has the fewest steps, ties to the lowest i; Nothing
+-- when no row has the class.
+data CoverSummary = CoverSummary
+  { csRowsOk       :: !Word64
+  , csRowsBailed   :: !Word64
+  , csRowsBad      :: !Word64
+  , csMatches      :: !Word64
+  , csCounts       :: [Word64]
+  , csWitness      :: [Maybe Word64]
+  , csWitnessSteps :: [Maybe Word32]
+  , csUnion        :: !Word32
+  } deriving (Show, Eq)
+
+-- | pxb_cover_query { all_mask, any_mask, none_mask, reserved = 0 }: a row
+-- matches when it is OK, has every class of 'cqAll', one of 'cqAny' (0: no
+-- such condition) and none of 'cqNone'.
+data CoverQuery = CoverQuery { cqAll :: !Word32, cqAny :: !Word32, cqNone :: !Word32 } deriving (Show, Eq)
+
+coverSummaryWords :: Int
+coverSummaryWords = 85                             -- sizeof(pxb_cover_summary) / 8
+
+-- | The 85 64-bit words of a pxb_cover_summary (little-endian host).
+coverSummary :: [Word64] -> CoverSummary
+coverSummary w =
+  let counts = take 32 (drop 4 w)
+      wit = take 32 (drop 36 w)
+      steps32 = concat [[fromIntegral (x .&. 0xFFFFFFFF), fromIntegral (x `shiftR` 32)] | x <- take 16 (drop 68 w)]
+      has = map (/= 0) counts
+      pick ok v = if ok then Just v else Nothing
+  in CoverSummary (w !! 0) (w !! 1) (w !! 2) (w !! 3) (take coverClasses counts)
+                  (take coverClasses (zipWith pick has wit)) (take coverClasses (zipWith pick has steps32))
+                  (fromIntegral ((w !! 84) .&. 0xFFFFFFFF))
+
+-- | pxb_cover: the coverage mask of every script row (docs/SEMANTICS.md §14):
+-- per row Nothing when its status is not OK, else its mask and outcome; and the
+-- call's summary, with row indices as witnesses.
+-- (additive to ABI 5: a library without the symbol fails to link)
+cover :: BatchConfig -> ScriptRows -> Int -> Word32 -> IO (Either String ([Maybe (Word32, Outcome)], CoverSummary))
+cover cfg rows n depth =
+  with cfg $ \pc ->
+    withArray rows $ \prows ->
+      allocaArray (max 1 n) $ \pm ->
+        allocaArray (max 1 n) $ \pst ->
+          allocaArray (max 1 (4 * n)) $ \pres ->
+            allocaArray coverSummaryWords $ \psum -> do
+              rc <- c_pxb_cover pc prows (fromIntegral n) depth pm pst pres psum
+              if rc /= 0
+                then Left <$> (c_pxb_strerror rc >>= peekCString)
+                else do
+                  ms <- peekArray n pm
+                  sts <- peekArray n pst
+                  summ <- coverSummary <$> peekArray coverSummaryWords psum
+                  per <- forM (zip3 [0 ..] ms sts) (\(i, m, st) ->
+                    if st /= 0
+                      then pure Nothing
+                      else do
+                        [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                        pure (Just (m, decode v t r f)))
+                  pure (Right (per, summ))
+
+-- | pxb_cover_range: the coverage of the plain instances first .. first + count - 1
+-- on the device, `chunk` ids at a time (0: 2^20); with a query, the first
+-- maxMatches matching (id, mask) pairs in ascending order and their total in
+-- 'csMatches'.  Witnesses are instance ids.  No output depends on the chunk.
+coverRange :: BatchConfig -> Word64 -> Word64 -> Word64 -> Maybe CoverQuery -> Int
+           -> IO (Either String (CoverSummary, [(Word64, Word32)]))
+coverRange cfg first count chunk mq maxMatches =
+  let nlist = maybe 0 (const maxMatches) mq
+      qw = maybe [0, 0, 0, 0] (\q -> [cqAll q, cqAny q, cqNone q, 0]) mq
+  in with cfg $ \pc ->
+    withArray qw $ \pq ->
+      allocaArray (max 1 nlist) $ \pids ->
+        allocaArray (max 1 nlist) $ \pmm ->
+          allocaArray coverSummaryWords $ \psum -> do
+            rc <- c_pxb_cover_range pc first count chunk (maybe nullPtr (const pq) mq) pids pmm (fromIntegral nlist) psum
+            if rc /= 0
+              then Left <$> (c_pxb_strerror rc >>= peekCString)
+              else do
+                summ <- coverSummary <$> peekArray coverSummaryWords psum
+                let m = min nlist (fromIntegral (csMatches summ))
+                ids <- peekArray m pids
+                mms <- peekArray m pmm
+                pure (Right (summ, zip ids mms))
 
 -- | What 'shrinkBatch' says of one instance (PXB_SHRINK_*).
 data ShrinkStatus = ShrinkMinimal | ShrinkBudget | ShrinkNotInput | ShrinkTooMany | ShrinkUnstable

@@ -14,7 +14,9 @@ never imported by this module.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import dataclasses
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -265,6 +267,9 @@ def load(path: str = LIB_PATH):
                         [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
                        ("pxb_trace_events",
                         [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_cover_device", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]),
+                       ("pxb_cover", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]),
+                       ("pxb_cover_range", [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, vp]),
                        ("pxb_shrink_batch_device",
                         [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
                        ("pxb_shrink_batch",
@@ -939,6 +944,259 @@ def trace_events_device(cfg: Config, d_rows, count: int, depth: int, d_offsets, 
     check(load().pxb_trace_events_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sel),
                                          _ptr(d_events) if capacity else None, capacity, _ptr(d_offsets),
                                          _ptr(d_status), _ptr(d_results), s))
+
+
+# ---- handler-path coverage (include/paxos_batch.h, docs/SEMANTICS.md §14) ----------
+COVER_NAMES = ("ASK_GRANT_EMPTY", "ASK_GRANT_STORED", "ASK_NACK", "PROPOSE_ACCEPT", "PROPOSE_NACK", "EXEC_APPLY",
+               "EXEC_IGNORED", "EXEC_PANIC", "DISCARD_DEAD", "DISCARD_ISOLATED", "Q1_FOREIGN_ACCEPT", "Q7_STALE_EXEC",
+               "TICK_START", "TICK_BUSY", "HAVE_IDLE", "HAVE_BELOW", "HAVE_RESTART_R1", "HAVE_ABORT_R2", "R1OK_STALE",
+               "R1OK_ACK", "R1OK_PROPOSE_OWN", "R1OK_PROPOSE_ADOPTED", "Q5_ADOPTED_OWN", "Q4_TIE", "R2S_DROPPED",
+               "R2S_ACK", "R2S_DONE", "R2S_RESTART", "R2S_REPEAT")
+COVER_CLASSES = len(COVER_NAMES)                     # PXB_COVER_CLASSES
+COVER_ALL = (1 << COVER_CLASSES) - 1
+COVER_BIT = {n: i for i, n in enumerate(COVER_NAMES)}    # name -> bit index (the index into a summary's lists)
+for _n, _i in COVER_BIT.items():                     # COVER_<NAME>: the mask, as PXB_COVER_<NAME>
+    globals()["COVER_" + _n] = 1 << _i
+# the quirk classes by their number in docs/SEMANTICS.md §9, as BIT INDICES: summary.witness[pxb.COVER_Q1]
+COVER_Q1, COVER_Q7, COVER_Q10, COVER_Q5, COVER_Q4, COVER_Q2 = 10, 11, 17, 22, 23, 28
+COVER_NONE = (1 << 64) - 1                           # a summary's witness of a class no row has
+COVER_RANGE_CHUNK = 1 << 20
+
+
+class pxb_cover_summary(C.Structure):
+    _fields_ = [("rows_ok", C.c_uint64), ("rows_bailed", C.c_uint64), ("rows_bad", C.c_uint64),
+                ("n_matches", C.c_uint64), ("count", C.c_uint64 * 32), ("witness", C.c_uint64 * 32),
+                ("witness_steps", C.c_uint32 * 32), ("union_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class pxb_cover_query(C.Structure):
+    _fields_ = [("all_mask", C.c_uint32), ("any_mask", C.c_uint32), ("none_mask", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+COVER_SUMMARY_BYTES = 680
+assert C.sizeof(pxb_cover_summary) == COVER_SUMMARY_BYTES and C.sizeof(pxb_cover_query) == 16
+
+
+@dataclasses.dataclass
+class CoverQuery:
+    """A row matches when it is TRACE_OK, has every class of all_mask, one of
+    any_mask (0: no such condition) and none of none_mask."""
+    all_mask: int = 0
+    any_mask: int = 0
+    none_mask: int = 0
+
+    def to_c(self):
+        return pxb_cover_query(self.all_mask, self.any_mask, self.none_mask, 0)
+
+    def matches(self, mask: int) -> bool:
+        return (mask & self.all_mask) == self.all_mask and (not self.any_mask or bool(mask & self.any_mask)) and \
+            not mask & self.none_mask
+
+
+class CoverSummary:
+    """pxb_cover_summary as Python values: rows_ok / rows_bailed / rows_bad /
+    n_matches, and per class (lists of COVER_CLASSES entries, indexed by bit)
+    `counts`, `witness` (row index or id of the OK row with the fewest steps,
+    ties to the lowest i; COVER_NONE when no row has the class) and
+    `witness_steps` (0xFFFFFFFF then); `union`, the classes some row has."""
+
+    def __init__(self, c):
+        self.rows_ok, self.rows_bailed, self.rows_bad = int(c.rows_ok), int(c.rows_bailed), int(c.rows_bad)
+        self.n_matches = int(c.n_matches)
+        self.counts = [int(c.count[b]) for b in range(COVER_CLASSES)]
+        self.witness = [int(c.witness[b]) for b in range(COVER_CLASSES)]
+        self.witness_steps = [int(c.witness_steps[b]) for b in range(COVER_CLASSES)]
+        self.union = int(c.union_mask)
+        self.tail = [(int(c.count[b]), int(c.witness[b]), int(c.witness_steps[b])) for b in range(COVER_CLASSES, 32)] + \
+            [int(c.reserved)]
+
+    def key(self):
+        return (self.rows_ok, self.rows_bailed, self.rows_bad, self.n_matches, self.counts, self.witness,
+                self.witness_steps, self.union, self.tail)
+
+    def __eq__(self, other):
+        return isinstance(other, CoverSummary) and self.key() == other.key()
+
+    def __repr__(self):
+        per = ", ".join("%s=%d" % (COVER_NAMES[b], n) for b, n in enumerate(self.counts) if n)
+        return "CoverSummary(ok=%d bailed=%d bad=%d matches=%d: %s)" % (self.rows_ok, self.rows_bailed, self.rows_bad,
+                                                                       self.n_matches, per)
+
+
+def cover_summary_from(buf) -> CoverSummary:
+    """A CoverSummary of the 680 bytes of a pxb_cover_summary (bytes, a numpy
+    array, or a CPU torch tensor)."""
+    if hasattr(buf, "numpy"):
+        buf = buf.numpy()
+    raw = bytes(buf if isinstance(buf, (bytes, bytearray)) else buf.tobytes())
+    if len(raw) != COVER_SUMMARY_BYTES:
+        raise ValueError("a pxb_cover_summary is %d bytes" % COVER_SUMMARY_BYTES)
+    return CoverSummary(pxb_cover_summary.from_buffer_copy(raw))
+
+
+def cover_names(mask: int):
+    """The names of the classes of a coverage mask, in bit order."""
+    return [n for i, n in enumerate(COVER_NAMES) if (int(mask) >> i) & 1]
+
+
+def cover_of_events(events, n_acceptors: int, per_event: bool = False):
+    """The coverage mask of ONE row's events (a structured array of
+    event_dtype(), all of the row's events in trace_events' order): the
+    specification of docs/SEMANTICS.md §14.  per_event: one mask per event."""
+    granted = [None] * n_acceptors
+    fresh = [False] * n_acceptors
+    log_len = [0] * n_acceptors
+    before, seen = {}, {}
+    out = []
+    for e in events:
+        i, peer, n_out, kind = int(e["index"]), int(e["peer"]), int(e["n_out"]), int(e["in"]["kind"])
+        m = 0
+        if e["actor"] == EVT_ACCEPTOR:
+            fate = int(e["fate"])
+            if fate == EVT_DISCARDED_DEAD:
+                m |= COVER_DISCARD_DEAD
+            elif fate == EVT_DISCARDED_ISOL:
+                m |= COVER_DISCARD_ISOLATED
+            else:
+                t_max, t_store, val, meta, _ = event_after_acc(e)
+                rk = int(e["out"][0]["kind"]) if n_out else None
+                if kind == 0:                           # AskForTicket
+                    if rk == 0:
+                        m |= COVER_ASK_GRANT_STORED if int(e["out"][0]["z"]) else COVER_ASK_GRANT_EMPTY
+                        granted[i] = peer
+                    else:
+                        m |= COVER_ASK_NACK
+                elif kind == 1:                         # Propose
+                    if rk == 2:
+                        m |= COVER_PROPOSE_ACCEPT
+                        if granted[i] != peer:
+                            m |= COVER_Q1_FOREIGN_ACCEPT
+                    else:
+                        m |= COVER_PROPOSE_NACK
+                else:                                   # Execute
+                    grew, dead = (meta & 0x7FFFFFFF) > log_len[i], bool(meta >> 31)
+                    if grew:
+                        m |= COVER_EXEC_APPLY
+                        if not fresh[i]:
+                            m |= COVER_Q7_STALE_EXEC
+                    if dead:
+                        m |= COVER_EXEC_PANIC
+                    if not grew and not dead:
+                        m |= COVER_EXEC_IGNORED
+                fresh[i] = val != 0 and t_store == t_max
+                log_len[i] = meta & 0x7FFFFFFF
+        else:
+            after = event_after_prop(e)
+            b_ticket, _, _, b_state, b_mr_t, b_mr_v, _, _ = before.get(i, (0,) * 8)
+            ticket, cmd, acks, state, mr_t, mr_v, r2_v, pending = after
+            if peer == EVT_PEER_TICK:
+                m |= COVER_TICK_START if n_out else COVER_TICK_BUSY
+            elif kind == 1:                             # HaveTicket
+                if b_state == 0:
+                    m |= COVER_HAVE_IDLE
+                elif not n_out:
+                    m |= COVER_HAVE_BELOW
+                else:
+                    m |= COVER_HAVE_RESTART_R1 if b_state == 1 else COVER_HAVE_ABORT_R2
+            elif kind == 0:                             # Round1OK
+                if b_state != 1 or b_ticket != int(e["in"]["x"]):
+                    m |= COVER_R1OK_STALE
+                else:
+                    if not n_out:
+                        m |= COVER_R1OK_ACK
+                    elif not pending:
+                        m |= COVER_R1OK_PROPOSE_OWN
+                    else:
+                        m |= COVER_R1OK_PROPOSE_ADOPTED
+                        if r2_v == cmd:
+                            m |= COVER_Q5_ADOPTED_OWN
+                    if int(e["in"]["z"]) and b_mr_v and b_mr_t == int(e["in"]["y"]):
+                        m |= COVER_Q4_TIE
+            else:                                       # Round2Success
+                if b_state != 2:
+                    m |= COVER_R2S_DROPPED
+                else:
+                    m |= (COVER_R2S_ACK, COVER_R2S_DONE, COVER_R2S_RESTART)[n_out]
+                    s = seen.setdefault(i, set())
+                    if peer in s:
+                        m |= COVER_R2S_REPEAT
+                    s.add(peer)
+            if any(int(e["out"][j]["kind"]) == 1 for j in range(n_out)):      # a Propose goes out: a new Round 2
+                seen[i] = set()
+            before[i] = after
+        out.append(m)
+    if per_event:
+        return out
+    total = 0
+    for m in out:
+        total |= m
+    return total
+
+
+def cover(cfg: Config, rows, depth: int):
+    """pxb_cover: the coverage mask of every script row.  Returns (masks uint32
+    (n,), status uint32 (n,), results uint32 (n, 4), summary CoverSummary); a row
+    that is not TRACE_OK has mask 0 and a zeroed result; summary.witness holds
+    row indices."""
+    import numpy as np
+    rows = _script_rows(cfg, rows, depth)
+    n = len(rows)
+    masks = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.uint32)
+    res = np.zeros((n, 4), dtype=np.uint32)
+    c = cfg.to_c(0, 1)
+    s = pxb_cover_summary()
+    check(load().pxb_cover(C.byref(c), _ptr(rows) if n else None, n, depth, _ptr(masks) if n else None,
+                           _ptr(status) if n else None, _ptr(res) if n else None, C.byref(s)))
+    return masks, status, res, CoverSummary(s)
+
+
+def cover_ids(cfg: Config, ids):
+    """cover of the plain instances `ids`: all-keep rows at depth 0."""
+    return cover(cfg, scripts_empty(cfg, ids, 0), 0)
+
+
+def cover_device(cfg: Config, d_rows, count: int, depth: int, d_masks=None, d_status=None, d_results=None,
+                 d_summary=None, stream=None):
+    """pxb_cover_device on torch tensors, asynchronous on `stream`: d_rows uint8,
+    d_masks int32 (count,), d_status int32 (count,), d_results int32 (count, 4),
+    d_summary uint8 (680,) (8-byte aligned; read it back with
+    cover_summary_from after a synchronise); every output optional."""
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_masks", d_masks, count, 4)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    if d_summary is not None:
+        _check_bytes("d_summary", d_summary, COVER_SUMMARY_BYTES)
+    c = cfg.to_c(0, 1)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_cover_device(C.byref(c), _ptr(d_rows), count, depth, _ptr(d_masks), _ptr(d_status),
+                                  _ptr(d_results), _ptr(d_summary), s))
+
+
+CoverRange = collections.namedtuple("CoverRange", "summary match_ids match_masks")
+
+
+def cover_range(cfg: Config, first: int, count: int, query: Optional[CoverQuery] = None, max_matches: int = 0,
+                chunk: int = 0):
+    """pxb_cover_range: the coverage of the plain instances first .. first + count
+    - 1 (ids wrap modulo 2^64), `chunk` ids at a time on the device (0: 2^20).
+    Returns CoverRange(summary, match_ids uint64, match_masks uint32): the
+    summary's witnesses are instance ids; with a query, summary.n_matches counts
+    every matching id and the lists hold the first max_matches in ascending
+    order of i.  No output depends on `chunk`."""
+    import numpy as np
+    ids = np.zeros(max_matches if query is not None else 0, dtype=np.uint64)
+    mm = np.zeros(len(ids), dtype=np.uint32)
+    c = cfg.to_c(0, 1)
+    s = pxb_cover_summary()
+    q = query.to_c() if query is not None else None
+    check(load().pxb_cover_range(C.byref(c), first & ((1 << 64) - 1), count, chunk, C.byref(q) if q is not None else None,
+                                 _ptr(ids) if len(ids) else None, _ptr(mm) if len(ids) else None, len(ids),
+                                 C.byref(s)))
+    m = min(int(s.n_matches), len(ids))
+    return CoverRange(CoverSummary(s), ids[:m], mm[:m])
 
 
 _REQ_NAMES = ("AskForTicket", "Propose", "Execute")

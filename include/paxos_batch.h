@@ -654,6 +654,92 @@ int pxb_trace_events(const pxb_config* cfg, const uint8_t* rows, uint64_t count,
                      const pxb_trace_sel* sel, pxb_trace_event* events, uint64_t capacity, uint64_t* offsets,
                      uint32_t* status, pxb_result* results, uint64_t* n_events);
 
+/* ---- handler-path coverage (additive to ABI 5, found by symbol) -----------------
+ * pxb_cover: which handler paths and reference quirks a script row exercised
+ * (docs/SEMANTICS.md §14).  The coverage mask of a row is the OR of the classes
+ * below over the row's events (pxb_trace_events); a row that is not
+ * PXB_TRACE_OK has mask 0, a zeroed result, and counts under rows_bailed /
+ * rows_bad only.  Each class depends on the event and on the earlier events of
+ * the same actor; the table with the exact conditions is §14's, and
+ * pxb.cover_of_events is its executable form.  Nothing is stored per event: the
+ * kernels run pxb_trace_events' lane and fold its events in registers.
+ *
+ * The summary: count[b] = the OK rows with class b; witness[b] = among those
+ * the row with the fewest steps (result.flags >> 16), ties to the lowest i: its
+ * row index (rows forms) or its instance id first + i (range form), with its
+ * steps in witness_steps[b]; both all ones (~0) when count[b] == 0, and for
+ * b >= PXB_COVER_CLASSES.  union_mask = the classes with count[b] != 0.
+ * Integer adds and minima only: the summary does not depend on the launch.
+ *
+ * pxb_cover_device: d_rows as pxb_trace_events_device takes them (count <=
+ * 2^30, pxb_script_stride(P, N, depth) apart, 8-byte aligned); d_masks,
+ * d_status, d_results (16-byte aligned) and d_summary (8-byte aligned) are all
+ * nullable.  Asynchronous on `stream`, no device synchronisation, no
+ * allocation.  n_matches is 0.  count == 0 gives the empty summary.
+ * pxb_cover: the same over host buffers.
+ *
+ * pxb_cover_range: the plain instances first + i, i < count (ids wrap modulo
+ * 2^64), run as all-keep rows at depth 0 in chunks of `chunk` ids (0: 2^20; at
+ * most 2^30); device memory is one chunk of rows, masks and status from the
+ * stream-ordered pool plus the match list, whatever `count` is.  With a query q,
+ * a row MATCHES when it is PXB_TRACE_OK, (m & all_mask) == all_mask, any_mask
+ * == 0 or (m & any_mask) != 0, and (m & none_mask) == 0; n_matches counts every
+ * match and match_ids / match_masks (nullable; match_ids required when
+ * max_matches > 0) get the first max_matches in ascending i.  q == NULL: no
+ * list, n_matches = 0.  No output depends on `chunk`.
+ *
+ * PXB_E_INVAL, decided before any device call: a null cfg, null rows with
+ * count > 0, count > 2^30 (rows forms), chunk > 2^30, depth > 4096, a misaligned
+ * device pointer, q->reserved != 0, PXB_CFG_TRACE_PRODUCTION, and every config
+ * pxb_trace_instance rejects.  The host forms then return PXB_E_NODEV without
+ * a GPU.                                                                       */
+#define PXB_COVER_CLASSES 29
+#define PXB_COVER_ASK_GRANT_EMPTY      (1u << 0)   /* acceptor: Ask -> Round1OK(Nothing)            */
+#define PXB_COVER_ASK_GRANT_STORED     (1u << 1)   /* Ask -> Round1OK with a stored proposal         */
+#define PXB_COVER_ASK_NACK             (1u << 2)   /* Ask -> HaveTicket                              */
+#define PXB_COVER_PROPOSE_ACCEPT       (1u << 3)   /* Propose -> Round2Success                       */
+#define PXB_COVER_PROPOSE_NACK         (1u << 4)   /* Propose -> HaveTicket                          */
+#define PXB_COVER_EXEC_APPLY           (1u << 5)   /* Execute, the log grew                          */
+#define PXB_COVER_EXEC_IGNORED         (1u << 6)   /* Execute, alive after, log unchanged            */
+#define PXB_COVER_EXEC_PANIC           (1u << 7)   /* Execute, dead after (Q6)                       */
+#define PXB_COVER_DISCARD_DEAD         (1u << 8)   /* discarded: dead                                */
+#define PXB_COVER_DISCARD_ISOLATED     (1u << 9)   /* discarded: isolated                            */
+#define PXB_COVER_Q1_FOREIGN_ACCEPT    (1u << 10)  /* accepted from a proposer it did not grant last */
+#define PXB_COVER_Q7_STALE_EXEC        (1u << 11)  /* applied a proposal that was not fresh          */
+#define PXB_COVER_TICK_START           (1u << 12)  /* proposer: Tick with an output                  */
+#define PXB_COVER_TICK_BUSY            (1u << 13)  /* Tick without one                               */
+#define PXB_COVER_HAVE_IDLE            (1u << 14)  /* HaveTicket, before Idle                        */
+#define PXB_COVER_HAVE_BELOW           (1u << 15)  /* HaveTicket, before not Idle, no output         */
+#define PXB_COVER_HAVE_RESTART_R1      (1u << 16)  /* HaveTicket with output, before Round1          */
+#define PXB_COVER_HAVE_ABORT_R2        (1u << 17)  /* HaveTicket with output, before Round2 (Q10)    */
+#define PXB_COVER_R1OK_STALE           (1u << 18)  /* Round1OK not counted                           */
+#define PXB_COVER_R1OK_ACK             (1u << 19)  /* counted, no output                             */
+#define PXB_COVER_R1OK_PROPOSE_OWN     (1u << 20)  /* counted, Propose, after.pending == 0           */
+#define PXB_COVER_R1OK_PROPOSE_ADOPTED (1u << 21)  /* counted, Propose, after.pending != 0           */
+#define PXB_COVER_Q5_ADOPTED_OWN       (1u << 22)  /* bit 21 with after.r2_v == after.cmd            */
+#define PXB_COVER_Q4_TIE               (1u << 23)  /* counted Round1OK whose ticket ties the MostRecent */
+#define PXB_COVER_R2S_DROPPED          (1u << 24)  /* Round2Success, before not Round2               */
+#define PXB_COVER_R2S_ACK              (1u << 25)  /* counted, no output                             */
+#define PXB_COVER_R2S_DONE             (1u << 26)  /* counted, Execute                               */
+#define PXB_COVER_R2S_RESTART          (1u << 27)  /* counted, Execute then AskForTicket             */
+#define PXB_COVER_R2S_REPEAT           (1u << 28)  /* counted twice from one acceptor in one Round 2 (Q2/Q3) */
+typedef struct pxb_cover_summary {    /* 680 B, no implicit padding */
+  uint64_t rows_ok, rows_bailed, rows_bad, n_matches;
+  uint64_t count[32];          /* OK rows with class b                                   */
+  uint64_t witness[32];        /* row index (rows form) or global id (range form) of the  */
+  uint32_t witness_steps[32];  /* OK row with class b that has the fewest steps, lowest i */
+  uint32_t union_mask, reserved;       /* among those; ~0 / 0xFFFFFFFF when count[b] == 0 */
+} pxb_cover_summary;
+typedef struct pxb_cover_query { uint32_t all_mask, any_mask, none_mask, reserved; } pxb_cover_query;
+int pxb_cover_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                     uint32_t* d_masks, uint32_t* d_status, pxb_result* d_results,
+                     pxb_cover_summary* d_summary, void* stream);
+int pxb_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+              uint32_t* masks, uint32_t* status, pxb_result* results, pxb_cover_summary* summary);
+int pxb_cover_range(const pxb_config* cfg, uint64_t first, uint64_t count, uint64_t chunk /* 0: default 2^20 */,
+                    const pxb_cover_query* q /* nullable: no list */, uint64_t* match_ids, uint32_t* match_masks,
+                    uint64_t max_matches, pxb_cover_summary* summary);
+
 /* ---- batched shrinker (additive to ABI 5, found by symbol like the queries) ----
  * Many failing schedules reduced to 1-minimal fault sets at once, everything on
  * the device (docs/SEMANTICS.md §11).  Row i of d_rows (fully explicit rows, as
