@@ -19,7 +19,9 @@
 //   the cursor kernel and the scatter kernel of paxos_query.hip's list, over
 //     the flag bytes: ascending g from the caller's cursor, below `capacity`.
 // Everything is sized from count x T: the device form never synchronises.  No
-// block waits for another; plain vector stores only.
+// block waits for another; plain vector stores only.  All but the candidate
+// kernel live in explore_list.h, which pxb_explore_cover
+// (paxos_explore_cover.hip) shares.
 //
 // Built as three units by proposer count (-DPXB_EXP_P=1|2|3) so that the slow
 // device compiles overlap; the unit of P = 1 also holds the other kernels and
@@ -109,116 +111,13 @@ exp_ptr exp_pick<PXB_EXP_P>(const pxb_config* cfg) { return lane_shape(cfg, ExpK
 }  // namespace pxb
 
 #if PXB_EXP_P == 1
-#include "host_util.h"
+#include "explore_list.h"
 
 extern "C" uint64_t explore_chunk_hook(void);   // paxos_batch.hip: PXB_EXPLORE_CHUNK
 
 namespace pxx {
 using namespace pxb::ev;
 using namespace pxb::host;
-
-constexpr int XBLOCK = 256;                       // candidates per tile of the list (4 waves)
-constexpr int XWAVES = XBLOCK / 64;
-constexpr uint64_t MAX_CALL = 1ull << 32;         // candidates of one device call
-
-struct ExpList {
-  ExploreSpace e;
-  const uint8_t* rows;
-  uint64_t stride;
-  uint64_t total;
-  uint32_t P;                       // the call's proposer count
-  uint32_t sel;                     // the listed bit: EXP_MINIMAL or EXP_HELD
-  uint8_t* bytes;
-  uint32_t* tcount;                 // listed candidates per tile
-  uint32_t* counts;                 // count * 4 * 3, zeroed (nullable)
-  uint32_t* status;                 // count (nullable)
-};
-
-__device__ __forceinline__ uint32_t block_sum(uint32_t wave_value, uint32_t* s_w) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  if (lane == 0u) s_w[w] = wave_value;
-  __syncthreads();
-  uint32_t t = 0u;
-#pragma unroll
-  for (int j = 0; j < XWAVES; ++j) t += s_w[j];
-  return t;
-}
-
-__global__ __launch_bounds__(XBLOCK) void explore_minimal_kernel(ExpList k) {
-  __shared__ uint32_t s_w[XWAVES];
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t g = (uint64_t)blockIdx.x * XBLOCK + threadIdx.x;
-  const bool in = g < k.total;
-  uint32_t f = 0u, key = 0u;
-  if (in) {
-    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
-    key = i * 4u + explore_radius(k.e, c);
-    f = k.bytes[g];
-    // (the other candidates' held bits are final: this kernel only ever adds the minimal bit)
-    if ((f & EXP_HELD) && explore_is_minimal(k.e, explore_unrank(k.e, c), k.bytes + (uint64_t)i * tt)) {
-      f |= EXP_MINIMAL;
-      k.bytes[g] = (uint8_t)f;
-    }
-    if (c == 0u && k.status)
-      k.status[i] = explore_parent_bad(k.rows + (uint64_t)i * k.stride, k.P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
-  }
-  if (k.counts) {
-    // {ran OK, held, minimal} per (parent, radius): one add per distinct key of the wave and column
-    unsigned long long act = __ballot(f != 0u);
-    while (act != 0ull) {                         // (wave-uniform)
-      const int lead = __ffsll(act) - 1;
-      const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-      const bool same = (f != 0u) & (key == k0);
-      const uint32_t n0 = (uint32_t)__popcll(__ballot(same & ((f & EXP_RAN) != 0u)));
-      const uint32_t n1 = (uint32_t)__popcll(__ballot(same & ((f & EXP_HELD) != 0u)));
-      const uint32_t n2 = (uint32_t)__popcll(__ballot(same & ((f & EXP_MINIMAL) != 0u)));
-      if ((int)lane == lead) {
-        uint32_t* const o = k.counts + (uint64_t)k0 * 3u;
-        if (n0) atomicAdd(o, n0);
-        if (n1) atomicAdd(o + 1, n1);
-        if (n2) atomicAdd(o + 2, n2);
-      }
-      act &= ~__ballot(same);
-    }
-  }
-  const uint32_t n = block_sum((uint32_t)__popcll(__ballot((f & k.sel) != 0u)), s_w);
-  if (threadIdx.x == 0u) k.tcount[blockIdx.x] = n;
-}
-
-// the list's base for this call = the caller's cursor; cursor += the call's matches
-__global__ void explore_cursor_kernel(uint64_t* __restrict__ cursor, const uint32_t* __restrict__ tcount,
-                                      const uint64_t* __restrict__ toff, uint64_t ntiles,
-                                      uint64_t* __restrict__ list_base) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const uint64_t b = *cursor;
-    *list_base = b;
-    *cursor = b + toff[ntiles - 1] + tcount[ntiles - 1];
-  }
-}
-
-__global__ __launch_bounds__(XBLOCK) void explore_scatter_kernel(const uint8_t* __restrict__ bytes, uint64_t total,
-                                                                 uint32_t sel, uint64_t first_g,
-                                                                 const uint32_t* __restrict__ tcount,
-                                                                 const uint64_t* __restrict__ toff,
-                                                                 const uint64_t* __restrict__ list_base,
-                                                                 uint64_t* __restrict__ ids, uint64_t capacity) {
-  __shared__ uint32_t s_w[XWAVES];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  // (both block-uniform) no listed candidate in the tile, or the list is full
-  if (tcount[blockIdx.x] == 0u) return;
-  const uint64_t pos = *list_base + toff[blockIdx.x];
-  if (pos >= capacity) return;
-  const uint64_t g = (uint64_t)blockIdx.x * XBLOCK + threadIdx.x;
-  const bool m = g < total && (bytes[g] & sel) != 0u;
-  const unsigned long long bal = __ballot(m);
-  if (lane == 0u) s_w[w] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = 0u;
-#pragma unroll
-  for (int j = 0; j < XWAVES; ++j) before += (j < (int)w) ? s_w[j] : 0u;
-  const uint64_t at = pos + before + (uint64_t)__popcll(bal & ((1ull << lane) - 1ull));
-  if (m && at < capacity) ids[at] = first_g + g;
-}
 
 struct ExpPick {
   const pxb_config* cfg;
@@ -229,17 +128,9 @@ static int pick(const pxb_config* cfg, exp_ptr* fn) {
   *fn = lane_proposers(cfg, ExpPick{cfg}, (exp_ptr) nullptr);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
-// the space of a call (T = 0: none)
-static ExploreSpace space_of(const pxb_config* cfg, uint32_t site_depth, uint32_t radius) {
-  return explore_space(explore_sites(cfg->n_proposers, cfg->n_acceptors, site_depth), cfg->delay_max, radius);
-}
-// the rules of a row's space: pxb_explore_row's, and part of the calls'
 static int validate_space(const pxb_config* cfg, uint32_t depth, const pxb_explore_space* sp, ExploreSpace* e) {
-  if (!cfg || !sp || depth > PXB_SCRIPT_MAX_DEPTH) return PXB_E_INVAL;
-  if (sp->site_depth == 0u || sp->site_depth > depth || sp->radius > PXB_EXPLORE_MAX_RADIUS) return PXB_E_INVAL;
-  if (!trace_config_ok(cfg)) return PXB_E_INVAL;
-  *e = space_of(cfg, sp->site_depth, sp->radius);
-  return e->T ? PXB_OK : PXB_E_INVAL;
+  if (!sp) return PXB_E_INVAL;
+  return validate_space_of(cfg, depth, sp->site_depth, sp->radius, e);
 }
 // the argument rules both calls share
 static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,
@@ -292,21 +183,10 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
   if (int rc = current_device(&dev)) return rc;
   if (count == 0) return PXB_OK;
 
-  const uint64_t total = count * e.T, ntiles = (total + XBLOCK - 1) / XBLOCK;
-  size_t scan_b = 0;
-  if (hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, widen_iter(nullptr, Widen{}), (uint64_t*)nullptr,
-                                                      (int64_t)ntiles, st))
-    return hip_fail(e);
-  // the call's scratch: list base | flag bytes | tile counts | tile offsets | scan
-  const size_t bytes_b = pad256((size_t)total), cnt_b = pad256((size_t)(ntiles * 4u)), off_b = pad256((size_t)(ntiles * 8u));
-  char* buf = nullptr;
-  if (int rc = pxw::scratch(dev, 256u + bytes_b + cnt_b + off_b + scan_b, st, reinterpret_cast<void**>(&buf)))
-    return rc;
-  uint64_t* const list_base = reinterpret_cast<uint64_t*>(buf);
-  uint8_t* const bytes = reinterpret_cast<uint8_t*>(buf + 256u);
-  uint32_t* const tcount = reinterpret_cast<uint32_t*>(buf + 256u + bytes_b);
-  uint64_t* const toff = reinterpret_cast<uint64_t*>(buf + 256u + bytes_b + cnt_b);
-  void* const scan_tmp = buf + 256u + bytes_b + cnt_b + off_b;
+  const uint64_t total = count * e.T;
+  ExpScratch x;
+  if (int rc = explore_scratch(dev, total, st, &x)) return rc;
+  uint8_t* const bytes = x.bytes;
 
   ExpParams c{};
   c.p = make_params(cfg);
@@ -327,7 +207,7 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
   l.P = cfg->n_proposers;
   l.sel = (space->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
   l.bytes = bytes;
-  l.tcount = tcount;
+  l.tcount = x.tcount;
   l.counts = d_counts;
   l.status = d_status;
 
@@ -336,19 +216,9 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
     if (d_counts && (err = hipMemsetAsync(d_counts, 0, (size_t)(count * 12u * 4u), st)) != hipSuccess) break;
     hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63u) / 64u)), dim3(64), 0, st, c);
     if ((err = hipGetLastError()) != hipSuccess) break;
-    hipLaunchKernelGGL(explore_minimal_kernel, dim3((unsigned)ntiles), dim3(XBLOCK), 0, st, l);
-    if ((err = hipGetLastError()) != hipSuccess) break;
-    err = hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_b, widen_iter(tcount, Widen{}), toff, (int64_t)ntiles, st);
-    if (err != hipSuccess) break;
-    hipLaunchKernelGGL(explore_cursor_kernel, dim3(1), dim3(64), 0, st, d_n_matches, tcount, toff, ntiles, list_base);
-    if ((err = hipGetLastError()) != hipSuccess) break;
-    if (capacity) {
-      hipLaunchKernelGGL(explore_scatter_kernel, dim3((unsigned)ntiles), dim3(XBLOCK), 0, st, bytes, total, l.sel,
-                         first_parent * e.T, tcount, toff, list_base, d_ids, capacity);
-      err = hipGetLastError();
-    }
+    err = explore_list(l, x, first_parent * e.T, d_ids, capacity, d_n_matches, st);
   } while (0);
-  const hipError_t f = hipFreeAsync(buf, st);     // (stream-ordered: after the launches above)
+  const hipError_t f = hipFreeAsync(x.buf, st);   // (stream-ordered: after the launches above)
   if (err == hipSuccess) err = f;
   return (err == hipSuccess) ? PXB_OK : hip_fail(err);
 }

@@ -62,6 +62,8 @@ module PaxosBatch
   , shrinkBatch
   , Explored (..)
   , explore
+  , Reach (..)
+  , exploreCover
     -- * Result queries (which instances to trace, without the results on the host)
   , Query (..)
   , FlagMode (..)
@@ -216,6 +218,10 @@ foreign import ccall safe "pxb_shrink_batch"
 foreign import ccall safe "pxb_explore"
   c_pxb_explore :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word64 -> Word64
                 -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> IO CInt
+
+foreign import ccall safe "pxb_explore_cover"
+  c_pxb_explore_cover :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word64 -> Word64
+                      -> Ptr Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word32 -> IO CInt
 
 foreign import ccall safe "pxb_sweep"
   c_pxb_sweep :: Ptr BatchConfig -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64
@@ -807,6 +813,57 @@ explore cfg rows n depth siteDepth radius mask minimal capacity =
                             _         -> (0, 0, 0)
                       pure (Explored ((st :: Word32) == 0) (map triple [0 .. 3]))
                     pure (Right (ids, total, out))
+
+-- | pxb_explore_reach of one parent (162 words): per class (bit index, as
+-- 'coverClasses') the candidates that ran OK and have it at each radius 0..3,
+-- and the lowest such candidate ('Nothing': none); candidate 0's mask; the
+-- classes some candidate has.  The radius of 'reachFirst' is the class's reach
+-- distance from the parent.
+data Reach = Reach
+  { reachCounts :: [[Word32]]
+  , reachFirst  :: [Maybe Word32]
+  , reachParent :: !Word32
+  , reachUnion  :: !Word32
+  } deriving (Show, Eq)
+
+-- | pxb_explore_cover: 'explore' with the coverage classes of every candidate
+-- (docs/SEMANTICS.md §15).  A candidate holds when it ran OK, has one of the
+-- outcome flags of @mask@ (0: no such condition) and its coverage mask matches
+-- the query (as 'coverRange'; @CoverQuery 0 0 0@: any).  Lists as 'explore'; with
+-- the list one 'Explored' and one 'Reach' a row.
+-- (additive to ABI 5: a library without the symbol fails to link)
+exploreCover :: BatchConfig -> ScriptRows -> Int -> Word32 -> Word32 -> Word32 -> CoverQuery -> Word32
+             -> Bool -> Int -> IO (Either String ([Word64], Word64, [Explored], [Reach]))
+exploreCover cfg rows n depth siteDepth radius (CoverQuery qAll qAny qNone) mask minimal capacity =
+  with cfg $ \pc ->
+    withArray rows $ \prows ->
+      withArray [siteDepth, radius, mask, if minimal then 1 else 0, qAll, qAny, qNone, 0] $ \pspace ->
+        allocaArray (max 1 capacity) $ \pids ->
+          allocaArray 1 $ \pn ->
+            allocaArray (max 1 (12 * n)) $ \pcnt ->
+              allocaArray (max 1 (162 * n)) $ \prch ->
+                allocaArray (max 1 n) $ \pst -> do
+                  rc <- c_pxb_explore_cover pc prows (fromIntegral n) depth pspace
+                                            (if capacity > 0 then pids else nullPtr) (fromIntegral capacity) pn pcnt
+                                            prch pst
+                  if rc /= 0
+                    then Left <$> (c_pxb_strerror rc >>= peekCString)
+                    else do
+                      [total] <- peekArray 1 pn
+                      ids <- peekArray (min capacity (fromIntegral total)) pids
+                      sts <- peekArray n pst
+                      out <- forM (zip [0 ..] sts) $ \(i, st) -> do
+                        ws <- peekArray 12 (advancePtr pcnt (12 * i))
+                        let triple r = case map fromIntegral (take 3 (drop (3 * r) ws)) of
+                              [a, b, c] -> (a, b, c)
+                              _         -> (0, 0, 0)
+                        pure (Explored ((st :: Word32) == 0) (map triple [0 .. 3]))
+                      reach <- forM [0 .. n - 1] $ \i -> do
+                        rw <- peekArray 162 (advancePtr prch (162 * i))
+                        let row r = take 29 (drop (32 * r) rw)
+                            firsts = [if f == maxBound then Nothing else Just f | f <- take 29 (drop 128 rw)]
+                        pure (Reach (map row [0 .. 3]) firsts (rw !! 160) (rw !! 161))
+                      pure (Right (ids, total, out, reach))
 
 -- | pxb_query.flag_mode: how (flags .&. mask) is tested.
 data FlagMode = AnyOf | AllOf | NoneOf

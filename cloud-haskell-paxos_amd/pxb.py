@@ -277,7 +277,10 @@ def load(path: str = LIB_PATH):
                        ("pxb_explore_row", [vp, C.c_uint32, vp, vp, C.c_uint64, vp]),
                        ("pxb_explore_device",
                         [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]),
-                       ("pxb_explore", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp])):
+                       ("pxb_explore", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp]),
+                       ("pxb_explore_cover_device",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+                       ("pxb_explore_cover", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
     lib.pxb_explore_total.argtypes = [C.c_uint32] * 5
@@ -1722,6 +1725,149 @@ def explore_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int,
     check(load().pxb_explore_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sp), first_parent,
                                     _ptr(d_ids) if capacity else None, capacity, _ptr(d_n_matches), _ptr(d_counts),
                                     _ptr(d_status), s))
+
+
+# ---- coverage of an exploration (include/paxos_batch.h, docs/SEMANTICS.md §15) ----
+class pxb_explore_reach(C.Structure):
+    _fields_ = [("count", (C.c_uint32 * 32) * 4), ("first", C.c_uint32 * 32), ("parent_mask", C.c_uint32),
+                ("union_mask", C.c_uint32)]
+
+
+class pxb_explore_cover_space(C.Structure):
+    _fields_ = [("site_depth", C.c_uint32), ("radius", C.c_uint32), ("flag_mask", C.c_uint32), ("flags", C.c_uint32),
+                ("q", pxb_cover_query)]
+
+
+EXPLORE_REACH_BYTES = 648
+REACH_NONE = 0xFFFFFFFF                              # a record's `first` of a class no candidate has
+assert C.sizeof(pxb_explore_reach) == EXPLORE_REACH_BYTES and C.sizeof(pxb_explore_cover_space) == 32
+
+
+def reach_dtype():
+    """A pxb_explore_reach as a numpy structured dtype (648 bytes)."""
+    import numpy as np
+    return np.dtype([("count", np.uint32, (4, 32)), ("first", np.uint32, (32,)), ("parent_mask", np.uint32),
+                     ("union_mask", np.uint32)])
+
+
+@dataclasses.dataclass
+class ExploreReach:
+    """pxb_explore_reach as Python values: counts[r][b], the candidates of radius
+    r that ran OK and have class b (bit index b, as COVER_BIT); first[b], the
+    lowest such candidate c or REACH_NONE; parent_mask, candidate 0's mask;
+    union, the classes with any count.  `tail`: what lies at b >= COVER_CLASSES
+    (zero counts, REACH_NONE firsts)."""
+    counts: list
+    first: list
+    parent_mask: int
+    union: int
+    tail: list
+
+    @classmethod
+    def from_record(cls, rec):
+        cnt, fst = rec["count"], rec["first"]
+        return cls([[int(cnt[r][b]) for b in range(COVER_CLASSES)] for r in range(4)],
+                   [int(fst[b]) for b in range(COVER_CLASSES)], int(rec["parent_mask"]), int(rec["union_mask"]),
+                   [[int(cnt[r][b]) for r in range(4)] + [int(fst[b])] for b in range(COVER_CLASSES, 32)])
+
+    def by_name(self):
+        """{class name: (first, [count per radius])} of the reached classes."""
+        return {n: (self.first[b], [self.counts[r][b] for r in range(4)]) for b, n in enumerate(COVER_NAMES)
+                if (self.union >> b) & 1}
+
+
+def explore_reach_of(masks, ran, S: int, A: int, radius: int):
+    """The reach record of ONE parent from its T candidates' coverage masks and
+    "ran OK" bits, in numpy: the specification of docs/SEMANTICS.md §15.  The
+    mask of a candidate that did not run OK counts as 0.  Returns a 0-d array of
+    reach_dtype()."""
+    import numpy as np
+    base = _explore_bases(S, A, radius)
+    masks = np.where(np.asarray(ran, dtype=bool), np.asarray(masks, dtype=np.uint32), np.uint32(0))
+    if masks.shape != (base[-1],):
+        raise ValueError("masks: one per candidate (%d)" % base[-1])
+    rec = np.zeros((), dtype=reach_dtype())
+    rec["first"][:] = REACH_NONE
+    for b in range(COVER_CLASSES):
+        has = ((masks >> np.uint32(b)) & np.uint32(1)) != 0
+        for r in range(radius + 1):
+            rec["count"][r, b] = int(has[base[r]:base[r + 1]].sum())
+        if has.any():
+            rec["first"][b] = int(np.argmax(has))
+            rec["union_mask"] |= np.uint32(1 << b)
+    rec["parent_mask"] = masks[0]
+    return rec
+
+
+def reach_distance(reach):
+    """The reach distance of every class from a record (an ExploreReach or a
+    reach_dtype() record): a list of COVER_CLASSES entries, the smallest radius
+    at which some candidate has the class, or None."""
+    if not isinstance(reach, ExploreReach):
+        reach = ExploreReach.from_record(reach)
+    return [next((r for r in range(4) if reach.counts[r][b]), None) for b in range(COVER_CLASSES)]
+
+
+def _explore_cover_space(site_depth, radius, query, flag_mask, minimal):
+    q = query.to_c() if query is not None else pxb_cover_query(0, 0, 0, 0)
+    return pxb_explore_cover_space(site_depth, radius, flag_mask, EXPLORE_MINIMAL if minimal else 0, q)
+
+
+def explore_cover(cfg: Config, parents, depth: int, site_depth: int, radius: int, query: Optional[CoverQuery] = None,
+                  flag_mask: int = 0, minimal: bool = True, capacity=None):
+    """pxb_explore_cover: pxb.explore's space with pxb.cover's classes.  A
+    candidate holds when it ran OK, has one of the outcome flags of `flag_mask`
+    (0: no such condition) and its coverage mask matches `query` (None: any).
+    Returns (ids, n_matches, counts, reach, status) with ids, n_matches, counts
+    and status as pxb.explore and reach a list of ExploreReach, one per parent:
+    reach_distance(reach[i]) says how many changed link entries away from
+    parent i each handler class lies."""
+    import numpy as np
+    lib = load()
+    rows = _script_rows(cfg, parents, depth)
+    n = len(rows)
+    counts = np.zeros((n, 4, 3), dtype=np.uint32)
+    status = np.zeros(n, dtype=np.uint32)
+    reach = np.zeros(n, dtype=reach_dtype())
+    c = cfg.to_c(0, 1)
+    sp = _explore_cover_space(site_depth, radius, query, flag_mask, minimal)
+    nm = C.c_uint64(0)
+    head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sp))
+    tail = (C.byref(nm), _ptr(counts) if n else None, _ptr(reach) if n else None, _ptr(status) if n else None)
+    if capacity is None:
+        check(lib.pxb_explore_cover(*head, None, 0, *tail))
+        capacity = nm.value
+    ids = np.zeros(capacity, dtype=np.uint64)
+    if capacity:
+        check(lib.pxb_explore_cover(*head, _ptr(ids), capacity, *tail))
+    return ids[:min(nm.value, capacity)], nm.value, counts, [ExploreReach.from_record(r) for r in reach], status
+
+
+def explore_cover_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int, radius: int, d_n_matches,
+                         query: Optional[CoverQuery] = None, flag_mask: int = 0, d_ids=None, capacity: int = 0,
+                         d_counts=None, d_reach=None, d_status=None, first_parent: int = 0, minimal: bool = True,
+                         stream=None):
+    """pxb_explore_cover_device on torch tensors, asynchronous on `stream`, no
+    synchronisation: the buffers of explore_device, and d_reach uint8 (count *
+    648,) (8-byte aligned; after a synchronise, d_reach.cpu().numpy().view(
+    reach_dtype()) gives the records).  Sizes and dtypes are checked here."""
+    if d_n_matches is None:
+        raise ValueError("d_n_matches is required")
+    if capacity and d_ids is None:
+        raise ValueError("d_ids is required when capacity > 0")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_n_matches", d_n_matches, 1, 8)
+    _check_buf("d_ids", d_ids, capacity, 8)
+    _check_buf("d_counts", d_counts, 12 * count, 4)
+    _check_buf("d_status", d_status, count, 4)
+    if d_reach is not None:
+        _check_bytes("d_reach", d_reach, EXPLORE_REACH_BYTES * count)
+    c = cfg.to_c(0, 1)
+    sp = _explore_cover_space(site_depth, radius, query, flag_mask, minimal)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_explore_cover_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(sp), first_parent,
+                                          _ptr(d_ids) if capacity else None, capacity, _ptr(d_n_matches),
+                                          _ptr(d_counts), _ptr(d_reach), _ptr(d_status), s))
 
 
 def init(n_devices: int = 0):

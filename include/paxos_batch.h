@@ -881,6 +881,55 @@ int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint
                 const pxb_explore_space* space, uint64_t* ids, uint64_t capacity,
                 uint64_t* n_matches, uint32_t* counts, uint32_t* status);
 
+/* ---- coverage of an exploration (additive to ABI 5, found by symbol) -----------
+ * Which handler classes lie within `radius` changed link entries of a row
+ * (docs/SEMANTICS.md §15).  The space, its order, the sites, the alternatives,
+ * the skipped candidates and a bad parent are pxb_explore's, unchanged:
+ * pxb_explore_total and pxb_explore_row work on the ids this call lists.  A
+ * candidate RAN OK as there (status PXB_TRACE_OK and no link consumed more than
+ * `depth` entries); its MASK m is the coverage mask (PXB_COVER_*) of its run if
+ * it ran OK and 0 otherwise.  It HOLDS when it ran OK, flag_mask == 0 or
+ * result.flags & 0xFF & flag_mask != 0, and m matches the query q as in
+ * pxb_cover_range: (m & all_mask) == all_mask, any_mask == 0 or m & any_mask
+ * != 0, m & none_mask == 0.  With flag_mask != 0 and an all-zero q this is
+ * pxb_explore's predicate.  MINIMAL is pxb_explore's rule over this predicate.
+ * Per parent, one reach record of integer sums and minima (independent of the
+ * launch order and of the host form's chunking).  Candidates are ordered by
+ * radius, so the radius of first[b] is the reach distance of class b: the
+ * smallest r with count[r][b] != 0.                                            */
+typedef struct pxb_explore_reach {   /* 648 B, no implicit padding */
+  uint32_t count[4][32];            /* [r][b]: candidates of radius r that ran OK and have class b; 0 above `radius` */
+  uint32_t first[32];               /* the lowest candidate c (< T) with class b; 0xFFFFFFFF when none, and for b >= 29 */
+  uint32_t parent_mask;             /* candidate 0's mask (0 if it did not run OK) */
+  uint32_t union_mask;              /* the classes with any non-zero count */
+} pxb_explore_reach;
+typedef struct pxb_explore_cover_space {  /* 32 B */
+  uint32_t site_depth;              /* 1..depth                                    */
+  uint32_t radius;                  /* 0..PXB_EXPLORE_MAX_RADIUS                   */
+  uint32_t flag_mask;               /* PXB_F_* bits of the predicate; 0: no outcome condition */
+  uint32_t flags;                   /* PXB_EXPLORE_MINIMAL or 0                    */
+  pxb_cover_query q;                /* reserved must be 0                          */
+} pxb_explore_cover_space;
+
+/* pxb_explore_cover_device: DEVICE buffers, asynchronous on `stream`, no device
+ * synchronisation.  Ids, cursor, capacity, d_counts ({ran OK, held, minimal}
+ * per radius) and d_status exactly as pxb_explore_device, with the predicate
+ * above; d_reach (nullable, 8-byte aligned) takes `count` records, OVERWRITTEN;
+ * a bad parent's record has zero counts and masks and an all-ones `first`.
+ * Scratch as pxb_explore_device: 1 B per candidate + 12 B per 256.
+ * PXB_E_INVAL for everything pxb_explore_device refuses except flag_mask == 0,
+ * and for q.reserved != 0, a misaligned d_reach and PXB_CFG_TRACE_PRODUCTION.  */
+int pxb_explore_cover_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                             const pxb_explore_cover_space* space, uint64_t first_parent,
+                             uint64_t* d_ids, uint64_t capacity, uint64_t* d_n_matches,
+                             uint32_t* d_counts, pxb_explore_reach* d_reach, uint32_t* d_status, void* stream);
+/* pxb_explore_cover: HOST buffers, blocking, on the current device;
+ * PXB_E_NODEV without a GPU (checked after the validation).  Chunked as
+ * pxb_explore (whole parents per PXB_EXPLORE_CHUNK); no output depends on it.  */
+int pxb_explore_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                      const pxb_explore_cover_space* space, uint64_t* ids, uint64_t capacity,
+                      uint64_t* n_matches, uint32_t* counts, pxb_explore_reach* reach, uint32_t* status);
+
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
 int         pxb_last_hip_error(void);
