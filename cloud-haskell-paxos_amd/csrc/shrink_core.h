@@ -19,7 +19,9 @@
 // parameters with what one lane does before its run (ShrParams::begin: the lane
 // job of paxos_trace_core.h).  The walk over a
 // parent's entries (a 64-lane wave with ballots on the device, a loop on the
-// host) is the caller's.
+// host) is the caller's.  The draw source and the start are written over the
+// draw source beneath them, so that shrink_cover_core.h puts them on the tapped
+// one (pxb_shrink_cover_batch).
 #pragma once
 #include <stdint.h>
 
@@ -148,8 +150,10 @@ __host__ __device__ inline uint64_t shrink_fnv_begin(const uint8_t* row) { retur
 // ScriptDraws over (row, rank table, j): a link byte whose rank selects it
 // reads as 1.  The byte and the rank come from the same index, two loads that
 // do not wait for each other; a neutralised entry resolves as the override 1,
-// never as a Philox draw.
-struct ShrinkDraws : ScriptDraws {
+// never as a Philox draw.  Base: ScriptDraws, or a draw source on top of it
+// (shrink_cover_core.h: the tapped one).
+template <class Base>
+struct ShrinkDrawsOver : Base {
   const uint16_t* r_links;            // the table's link part, [dirn][p][a][k]
   uint32_t r_j;                       // the candidate's index among its parent's
   bool r_prefix;                      // ranks <= j (else == j)
@@ -158,7 +162,7 @@ struct ShrinkDraws : ScriptDraws {
     return r_prefix ? rank <= r_j : rank == r_j;  // (j < SHR_NONE: SHR_NONE is never selected)
   }
   struct RankedByte {
-    const ShrinkDraws& d;
+    const ShrinkDrawsOver& d;
     __host__ __device__ __forceinline__ uint32_t operator()(uint64_t i) const {
       const uint32_t b = d.s_links[i], r = d.r_links[i];
       return d.selects(r) ? 1u : b;
@@ -166,26 +170,33 @@ struct ShrinkDraws : ScriptDraws {
   };
   __host__ __device__ __forceinline__ uint4 source_draw(uint32_t lo, uint32_t hi, uint32_t c2, uint32_t c3,
                                                         const uint32_t (&rk)[20]) const {
-    return source_draw_over(lo, hi, c2, c3, rk, RankedByte{*this});
+    return this->source_draw_over(lo, hi, c2, c3, rk, RankedByte{*this});
   }
 };
+typedef ShrinkDrawsOver<ScriptDraws> ShrinkDraws;
 
 // script_begin for candidate j of the parent (row, table): the same rule for the
-// three skews and the N windows
-template <class Lane>
-__host__ __device__ __forceinline__ uint32_t shrink_begin(Lane& L, const EvParams& kp, uint32_t depth,
-                                                          const uint8_t* row, const uint16_t* table, uint32_t j,
-                                                          bool prefix) {
-  ShrinkDraws& D = L;
+// three skews and the N windows.  Draws: the lane's ShrinkDrawsOver.
+template <class Draws, class Lane>
+__host__ __device__ __forceinline__ uint32_t shrink_begin_over(Lane& L, const EvParams& kp, uint32_t depth,
+                                                               const uint8_t* row, const uint16_t* table, uint32_t j,
+                                                               bool prefix) {
+  Draws& D = L;
   D.r_links = table + 3u + Lane::S::N;
   D.r_j = j;
   D.r_prefix = prefix;
   struct Sel {
-    const ShrinkDraws& d;
+    const Draws& d;
     const uint16_t* t;
     __host__ __device__ __forceinline__ bool operator()(uint32_t i) const { return d.selects(t[i]); }
   };
   return script_begin_sel(L, kp, depth, row, Sel{D, table});
+}
+template <class Lane>
+__host__ __device__ __forceinline__ uint32_t shrink_begin(Lane& L, const EvParams& kp, uint32_t depth,
+                                                          const uint8_t* row, const uint16_t* table, uint32_t j,
+                                                          bool prefix) {
+  return shrink_begin_over<ShrinkDraws>(L, kp, depth, row, table, j, prefix);
 }
 
 // the predicate of an ended candidate: status, the result's flags word, and its
@@ -213,20 +224,27 @@ struct ShrParams {
   uint16_t* csent;                  // total * 2 P N (nullable)
   uint4* cres;                      // total (nullable)
 
+  // Starts the lane as candidate c (< total) of the launch: its status as
+  // shrink_begin gives it (PXB_SCRIPT_BAD: a malformed row, the lane not started)
+  template <class Draws, class Lane>
+  __host__ __device__ __forceinline__ uint32_t start(Lane& L, uint64_t c) const {
+    // the parent: the last i with offsets[i] <= c (offsets[0] = 0, offsets[count] = total > c)
+    uint64_t lo = 0u, hi = count;
+    while (hi - lo > 1u) {
+      const uint64_t mid = lo + ((hi - lo) >> 1);
+      if (offsets[mid] <= c) lo = mid;
+      else hi = mid;
+    }
+    const uint32_t j = (uint32_t)(c - offsets[lo]);
+    return shrink_begin_over<Draws>(L, p, depth, rows + lo * stride, table + lo * tstride, j, prefix != 0u);
+  }
+
   template <class Lane, class Trace>
   __host__ __device__ __forceinline__ bool begin(Lane& L, Trace& T, uint64_t c) const {
     T.begin_count(1u, 0u);          // (an empty window: no records are counted)
     bool run = c < total;
     if (run) {
-      // the parent: the last i with offsets[i] <= c (offsets[0] = 0, offsets[count] = total > c)
-      uint64_t lo = 0u, hi = count;
-      while (hi - lo > 1u) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (offsets[mid] <= c) lo = mid;
-        else hi = mid;
-      }
-      const uint32_t j = (uint32_t)(c - offsets[lo]);
-      const uint32_t st = shrink_begin(L, p, depth, rows + lo * stride, table + lo * tstride, j, prefix != 0u);
+      const uint32_t st = start<ShrinkDraws>(L, c);
       if (st != PXB_TRACE_OK) {     // a malformed row: not run
         T.status = st;
         run = false;

@@ -60,6 +60,7 @@ module PaxosBatch
   , ShrinkStatus (..)
   , Shrunk (..)
   , shrinkBatch
+  , shrinkCoverBatch
   , Explored (..)
   , explore
   , Reach (..)
@@ -214,6 +215,11 @@ foreign import ccall safe "pxb_cover_range"
 foreign import ccall safe "pxb_shrink_batch"
   c_pxb_shrink_batch :: Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Word32
                      -> Ptr Word32 -> Ptr Word32 -> Ptr Word32 -> Ptr Word16 -> Ptr Word32 -> Ptr Word64 -> IO CInt
+
+foreign import ccall safe "pxb_shrink_cover_batch"
+  c_pxb_shrink_cover_batch :: Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32
+                           -> Ptr Word32 -> Ptr Word32 -> Ptr Word32 -> Ptr Word16 -> Ptr Word32 -> Ptr Word64
+                           -> Ptr Word32 -> IO CInt
 
 foreign import ccall safe "pxb_explore"
   c_pxb_explore :: Ptr BatchConfig -> Ptr Word8 -> Word64 -> Word32 -> Ptr Word32 -> Ptr Word64 -> Word64
@@ -744,7 +750,33 @@ data Shrunk = Shrunk
 -- the device (docs/SEMANTICS.md §11); the shrunk rows and one 'Shrunk' each.
 -- (additive to ABI 5: a library without the symbol fails to link)
 shrinkBatch :: BatchConfig -> [Word64] -> Word32 -> Word32 -> Word32 -> IO (Either String (ScriptRows, [Shrunk]))
-shrinkBatch cfg ids depth mask maxLaunches = do
+shrinkBatch cfg ids depth mask maxLaunches =
+  fmap (\(rows, out, _) -> (rows, out)) <$>
+    shrinkCall cfg ids depth (\pc pids prows n pst pnf pla psent pres psig _ ->
+      c_pxb_shrink_batch pc pids prows n depth mask maxLaunches pst pnf pla psent pres psig)
+
+-- | pxb_shrink_cover_batch: 'shrinkBatch' over a coverage predicate
+-- (docs/SEMANTICS.md §16).  A run holds when it ended OK within @depth@, has one
+-- of the outcome flags of @mask@ (0: no such condition) and its coverage mask
+-- matches the query (as 'coverRange'; @CoverQuery 0 0 0@: any).  With the rows
+-- and one 'Shrunk' each, the coverage mask of every returned row's accepted run
+-- (bit index as 'coverClasses'; not an input: the given row's mask).
+-- (additive to ABI 5: a library without the symbol fails to link)
+shrinkCoverBatch :: BatchConfig -> [Word64] -> Word32 -> CoverQuery -> Word32 -> Word32
+                 -> IO (Either String (ScriptRows, [Shrunk], [Word32]))
+shrinkCoverBatch cfg ids depth (CoverQuery qAll qAny qNone) mask maxLaunches =
+  withArray [mask, maxLaunches, 0, 0, qAll, qAny, qNone, 0] $ \ppred ->
+    shrinkCall cfg ids depth (\pc pids prows n pst pnf pla psent pres psig pmask ->
+      c_pxb_shrink_cover_batch pc pids prows n depth ppred pst pnf pla psent pres psig pmask)
+
+-- What 'shrinkBatch' and 'shrinkCoverBatch' share: the buffers of @ids@ at
+-- @depth@ around one call, and its outputs read back (the masks: zeros where
+-- the call does not write them).
+shrinkCall :: BatchConfig -> [Word64] -> Word32
+           -> (Ptr BatchConfig -> Ptr Word64 -> Ptr Word8 -> Word64 -> Ptr Word32 -> Ptr Word32 -> Ptr Word32
+               -> Ptr Word16 -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> IO CInt)
+           -> IO (Either String (ScriptRows, [Shrunk], [Word32]))
+shrinkCall cfg ids depth call = do
   let n = length ids
       bytes = n * scriptStride cfg depth
       links = 2 * fromIntegral (bcProposers cfg) * fromIntegral (bcAcceptors cfg) :: Int
@@ -756,23 +788,24 @@ shrinkBatch cfg ids depth mask maxLaunches = do
             allocaArray (max 1 n) $ \pla ->
               allocaArray (max 1 (links * n)) $ \psent ->
                 allocaArray (max 1 (4 * n)) $ \pres ->
-                  allocaArray (max 1 n) $ \psig -> do
-                    rc <- c_pxb_shrink_batch pc pids prows (fromIntegral n) depth mask maxLaunches
-                                             pst pnf pla psent pres psig
-                    if rc /= 0
-                      then Left <$> (c_pxb_strerror rc >>= peekCString)
-                      else do
-                        rows <- peekArray bytes prows
-                        sts <- peekArray n pst
-                        nfs <- peekArray n pnf
-                        las <- peekArray n pla
-                        sigs <- peekArray n psig
-                        out <- forM (zip [0 ..] (zip (zip sts nfs) (zip las sigs))) $ \(i, ((st, nf), (la, sg))) -> do
-                          [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
-                          sent <- peekArray links (advancePtr psent (links * i))
-                          pure (Shrunk (toEnum (fromIntegral (st :: Word32))) (fromIntegral (nf :: Word32))
-                                       (fromIntegral (la :: Word32)) sent (decode v t r f) sg)
-                        pure (Right (rows, out))
+                  allocaArray (max 1 n) $ \psig ->
+                    withArray (replicate (max 1 n) 0) $ \pmask -> do
+                      rc <- call pc pids prows (fromIntegral n) pst pnf pla psent pres psig pmask
+                      if rc /= 0
+                        then Left <$> (c_pxb_strerror rc >>= peekCString)
+                        else do
+                          rows <- peekArray bytes prows
+                          sts <- peekArray n pst
+                          nfs <- peekArray n pnf
+                          las <- peekArray n pla
+                          sigs <- peekArray n psig
+                          masks <- peekArray n pmask
+                          out <- forM (zip [0 ..] (zip (zip sts nfs) (zip las sigs))) $ \(i, ((st, nf), (la, sg))) -> do
+                            [v, t, r, f] <- peekArray 4 (advancePtr pres (4 * i))
+                            sent <- peekArray links (advancePtr psent (links * i))
+                            pure (Shrunk (toEnum (fromIntegral (st :: Word32))) (fromIntegral (nf :: Word32))
+                                         (fromIntegral (la :: Word32)) sent (decode v t r f) sg)
+                          pure (Right (rows, out, masks))
 
 -- | One parent of an 'explore': whether its row was well formed, and for each
 -- radius 0..3 how many of its candidates (ran OK, held, are minimal).

@@ -280,7 +280,11 @@ def load(path: str = LIB_PATH):
                        ("pxb_explore", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp]),
                        ("pxb_explore_cover_device",
                         [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp]),
-                       ("pxb_explore_cover", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp])):
+                       ("pxb_explore_cover", [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+                       ("pxb_shrink_cover_batch_device",
+                        [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+                       ("pxb_shrink_cover_batch",
+                        [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp])):
         getattr(lib, name).argtypes = args
         getattr(lib, name).restype = C.c_int
     lib.pxb_explore_total.argtypes = [C.c_uint32] * 5
@@ -1373,18 +1377,28 @@ def shrink(cfg: Config, instance, flag_mask: int, runner=None, max_launches: int
     individually removable ones; the longest prefix that keeps the predicate is
     taken.  `runner(cfg, rows, depth) -> (results, status, sent)` defaults to
     run_scripted."""
-    import numpy as np
     runner = runner or _run_scripted_runner
+
+    def run(rows):
+        res, status, sent = runner(cfg, rows, depth)
+        ok = [bool(status[i] == TRACE_OK and (int(res[i][3]) & 0xFF & flag_mask) and int(sent[i].max()) <= depth)
+              for i in range(len(res))]
+        return ok, sent, [None] * len(ok)
+    return _shrink_rounds(cfg, instance, run, max_launches, depth)[:3]
+
+
+def _shrink_rounds(cfg: Config, instance, run, max_launches: int, depth: int):
+    """The rounds pxb.shrink and pxb.shrink_cover share (docs/SEMANTICS.md §10,
+    §16).  `run(rows) -> (holds, sent, extra)`: per candidate row whether its run
+    holds the predicate, its send counts, and anything of the run to hand back.
+    Returns (row, faults, launches, extra of the accepted run)."""
+    import numpy as np
     if isinstance(instance, (int, np.integer)):
         row = extract_schedule(cfg, [int(instance)], depth)
     else:
         row = _script_rows(cfg, instance, depth).copy()
     if len(row) != 1:
         raise ValueError("instance: one id or one row")
-
-    def holds(res, status, sent):
-        return [bool(status[i] == TRACE_OK and (int(res[i][3]) & 0xFF & flag_mask) and int(sent[i].max()) <= depth)
-                for i in range(len(res))]
 
     def settle(r, sent):
         # benign 1s past what the run consumed (entries it never read)
@@ -1394,37 +1408,70 @@ def shrink(cfg: Config, instance, flag_mask: int, runner=None, max_launches: int
         nz = (lk != 0) & (lk != SCRIPT_KEEP8)
         lk[nz] = np.minimum(lk[nz], cfg.delay_max)
 
-    res, status, sent = runner(cfg, row, depth)
+    ok, sent, extra = run(row)
     launches = 1
-    if not holds(res, status, sent)[0]:
+    if not ok[0]:
         raise ValueError("shrink: the instance does not satisfy the predicate within depth %d" % depth)
-    sent = np.array(sent[0])
+    sent, extra = np.array(sent[0]), extra[0]
     settle(row, sent)
     while True:
         faults = script_faults(cfg, row, depth, sent)
         if not faults or launches + 2 > max_launches:
-            return row[0], faults, launches
+            return row[0], faults, launches, extra
         cand = np.repeat(row, len(faults), axis=0)
         for i, f in enumerate(faults):
             script_neutralise(cfg, cand[i:i + 1], depth, f)
-        ok = holds(*runner(cfg, cand, depth))
+        ok = run(cand)[0]
         launches += 1
         removable = [f for f, o in zip(faults, ok) if o]
         if not removable:
-            return row[0], faults, launches             # 1-minimal: this launch is the proof
+            return row[0], faults, launches, extra      # 1-minimal: this launch is the proof
         cand = np.repeat(row, len(removable), axis=0)
         for i in range(len(removable)):
             for f in removable[:i + 1]:
                 script_neutralise(cfg, cand[i:i + 1], depth, f)
-        res, status, sent_c = runner(cfg, cand, depth)
+        ok, sent_c, extra_c = run(cand)
         launches += 1
-        ok = holds(res, status, sent_c)
         best = max((i for i, o in enumerate(ok) if o), default=None)
         if best is None:                                # (prefix 1 is launch 1's candidate: deterministic runs keep it)
             raise PaxosError("shrink: a candidate that held did not hold again")
         row = cand[best:best + 1].copy()
-        sent = np.array(sent_c[best])
+        sent, extra = np.array(sent_c[best]), extra_c[best]
         settle(row, sent)
+
+
+def _run_cover_runner(cfg, rows, depth):
+    res, _, _, status, sent = run_scripted(cfg, rows, depth, want_digests=False)
+    return res, status, sent, cover(cfg, rows, depth)[0]
+
+
+def shrink_cover(cfg: Config, instance, query: Optional["CoverQuery"], flag_mask: int = 0, runner=None,
+                 max_launches: int = 64, depth: int = 64):
+    """pxb.shrink over a coverage predicate (docs/SEMANTICS.md §16; this function
+    is the specification of pxb_shrink_cover_batch).
+
+    The predicate of a run: status TRACE_OK; flag_mask == 0 or (result.flags &
+    0xFF & flag_mask) != 0; the run's coverage mask (pxb.cover's) matches
+    `query` (None: the all-zero query) by CoverQuery.matches; and no link
+    consumed more than `depth` entries.  Everything else is pxb.shrink's.
+    Returns (row, faults, launches, mask): mask is the coverage mask of the
+    returned row's accepted run.  `runner(cfg, rows, depth) -> (results, status,
+    sent, masks)` defaults to run_scripted for the first three and cover for the
+    masks; `launches` counts rounds as pxb.shrink does, not device calls."""
+    q = query if query is not None else CoverQuery()
+    for name, m in (("all_mask", q.all_mask), ("any_mask", q.any_mask), ("none_mask", q.none_mask)):
+        if m & ~((1 << COVER_CLASSES) - 1):
+            raise ValueError("query.%s: bits 0..%d" % (name, COVER_CLASSES - 1))
+    if flag_mask & ~0xFF:
+        raise ValueError("flag_mask: the eight outcome flags")
+    runner = runner or _run_cover_runner
+
+    def run(rows):
+        res, status, sent, masks = runner(cfg, rows, depth)
+        ok = [bool(status[i] == TRACE_OK and (flag_mask == 0 or int(res[i][3]) & 0xFF & flag_mask)
+                   and q.matches(int(masks[i])) and int(sent[i].max()) <= depth) for i in range(len(res))]
+        return ok, sent, [int(m) for m in masks]
+    return _shrink_rounds(cfg, instance, run, max_launches, depth)
 
 
 # ---- the batched shrinker (include/paxos_batch.h, docs/SEMANTICS.md §11) --------
@@ -1466,6 +1513,19 @@ def shrink_batch(cfg: Config, instances, flag_mask: int, depth: int = 64, max_la
     uint16 (n, 2, P, N), results uint32 (n, 4), signature uint64 (n,)): per
     instance what shrink(cfg, instance, flag_mask, depth=depth,
     max_launches=max_launches) returns, with a status where it raises."""
+    ids, rows, out = _shrink_batch_buffers(cfg, instances, depth, chunk)
+    c = cfg.to_c(0, 1)
+    lib = load()
+    for a in range(0, len(rows), chunk):
+        m = min(chunk, len(rows) - a)
+        check(lib.pxb_shrink_batch(C.byref(c), _ptr(ids[a:]) if ids is not None else None, _ptr(rows[a:]), m, depth,
+                                   flag_mask, max_launches, *(_ptr(o[a:]) for o in out)))
+    return (rows, *out)
+
+
+def _shrink_batch_buffers(cfg, instances, depth, chunk):
+    """What shrink_batch and shrink_cover_batch share: the argument checks, and
+    (ids or None, rows, (status, n_faults, launches, sent, results, signature))."""
     import numpy as np
     if chunk < 1:
         raise ValueError("chunk: at least 1")
@@ -1479,20 +1539,9 @@ def shrink_batch(cfg: Config, instances, flag_mask: int, depth: int = 64, max_la
         ids = np.ascontiguousarray(inst, dtype=np.uint64).reshape(-1)
         rows = np.zeros((len(ids), script_stride(cfg, depth)), dtype=np.uint8)
     n, P, N = len(rows), cfg.n_proposers, cfg.n_acceptors
-    status = np.zeros(n, dtype=np.uint32)
-    n_faults = np.zeros(n, dtype=np.uint32)
-    launches = np.zeros(n, dtype=np.uint32)
-    sent = np.zeros((n, 2, P, N), dtype=np.uint16)
-    res = np.zeros((n, 4), dtype=np.uint32)
-    sig = np.zeros(n, dtype=np.uint64)
-    c = cfg.to_c(0, 1)
-    lib = load()
-    for a in range(0, n, chunk):
-        m = min(chunk, n - a)
-        check(lib.pxb_shrink_batch(C.byref(c), _ptr(ids[a:]) if ids is not None else None, _ptr(rows[a:]), m, depth,
-                                   flag_mask, max_launches, _ptr(status[a:]), _ptr(n_faults[a:]), _ptr(launches[a:]),
-                                   _ptr(sent[a:]), _ptr(res[a:]), _ptr(sig[a:])))
-    return rows, status, n_faults, launches, sent, res, sig
+    return ids, rows, (np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32),
+                       np.zeros((n, 2, P, N), dtype=np.uint16), np.zeros((n, 4), dtype=np.uint32),
+                       np.zeros(n, dtype=np.uint64))
 
 
 def shrink_batch_device(cfg: Config, d_rows, count: int, depth: int, flag_mask: int, max_launches: int = 64,
@@ -1516,6 +1565,65 @@ def shrink_batch_device(cfg: Config, d_rows, count: int, depth: int, flag_mask: 
     check(load().pxb_shrink_batch_device(C.byref(c), _ptr(d_rows), count, depth, flag_mask, max_launches,
                                          _ptr(d_status), _ptr(d_n_faults), _ptr(d_launches), _ptr(d_sent),
                                          _ptr(d_results), _ptr(d_signature), s))
+
+
+# ---- shrinking over a coverage predicate (include/paxos_batch.h, docs/SEMANTICS.md §16) ----
+class pxb_shrink_pred(C.Structure):
+    _fields_ = [("flag_mask", C.c_uint32), ("max_launches", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("q", pxb_cover_query)]
+
+
+assert C.sizeof(pxb_shrink_pred) == 32
+
+
+def _shrink_pred(query, flag_mask, max_launches):
+    q = query if query is not None else CoverQuery()
+    return pxb_shrink_pred(flag_mask, max_launches, (C.c_uint32 * 2)(0, 0), q.to_c())
+
+
+def shrink_cover_batch(cfg: Config, instances, query: Optional[CoverQuery], flag_mask: int = 0, depth: int = 64,
+                       max_launches: int = 64, chunk: int = 4096):
+    """pxb_shrink_cover_batch: pxb.shrink_cover for many instances at once, on
+    the device.  `instances`, `chunk` and the first seven returned arrays as
+    shrink_batch; returns (rows, status, n_faults, launches, sent, results,
+    signature, masks uint32 (n,)): masks[i] is the coverage mask of the returned
+    row's accepted run (NOT_INPUT / TOO_MANY: the given row's, as pxb.cover)."""
+    import numpy as np
+    ids, rows, out = _shrink_batch_buffers(cfg, instances, depth, chunk)
+    out += (np.zeros(len(rows), dtype=np.uint32),)
+    c = cfg.to_c(0, 1)
+    pred = _shrink_pred(query, flag_mask, max_launches)
+    lib = load()
+    for a in range(0, len(rows), chunk):
+        m = min(chunk, len(rows) - a)
+        check(lib.pxb_shrink_cover_batch(C.byref(c), _ptr(ids[a:]) if ids is not None else None, _ptr(rows[a:]), m,
+                                         depth, C.byref(pred), *(_ptr(o[a:]) for o in out)))
+    return (rows, *out)
+
+
+def shrink_cover_batch_device(cfg: Config, d_rows, count: int, depth: int, query: Optional[CoverQuery],
+                              flag_mask: int = 0, max_launches: int = 64, d_status=None, d_n_faults=None,
+                              d_launches=None, d_sent=None, d_results=None, d_signature=None, d_masks=None,
+                              stream=None):
+    """pxb_shrink_cover_batch_device on torch tensors: shrink_batch_device's
+    arguments with the predicate of shrink_cover, and d_masks int32 (count,);
+    every output optional.  Ordered on `stream`, which the call synchronises
+    once per launch."""
+    N, P = cfg.n_acceptors, cfg.n_proposers
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_status", d_status, count, 4)
+    _check_buf("d_n_faults", d_n_faults, count, 4)
+    _check_buf("d_launches", d_launches, count, 4)
+    _check_buf("d_sent", d_sent, 2 * P * N * count, 2)
+    _check_buf("d_results", d_results, 4 * count, 4)
+    _check_buf("d_signature", d_signature, count, 8)
+    _check_buf("d_masks", d_masks, count, 4)
+    c = cfg.to_c(0, 1)
+    pred = _shrink_pred(query, flag_mask, max_launches)
+    s = C.c_void_p(stream) if stream else None
+    check(load().pxb_shrink_cover_batch_device(C.byref(c), _ptr(d_rows), count, depth, C.byref(pred), _ptr(d_status),
+                                               _ptr(d_n_faults), _ptr(d_launches), _ptr(d_sent), _ptr(d_results),
+                                               _ptr(d_signature), _ptr(d_masks), s))
 
 
 def shrink_clusters(signature, status):

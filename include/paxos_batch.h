@@ -930,6 +930,49 @@ int pxb_explore_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count
                       const pxb_explore_cover_space* space, uint64_t* ids, uint64_t capacity,
                       uint64_t* n_matches, uint32_t* counts, pxb_explore_reach* reach, uint32_t* status);
 
+/* ---- shrinking over a coverage predicate (additive to ABI 5, found by symbol) ---
+ * pxb_shrink_batch with one change, the PREDICATE of a run (docs/SEMANTICS.md
+ * §16): status PXB_TRACE_OK; flag_mask == 0 or result.flags & 0xFF & flag_mask
+ * != 0; the run's coverage mask m (PXB_COVER_*, as pxb_cover gives it) matches q
+ * as in pxb_cover_range ((m & all_mask) == all_mask, any_mask == 0 or m &
+ * any_mask != 0, m & none_mask == 0); and no link consumed more than `depth`
+ * entries.  With flag_mask & 0xFF != 0 and an all-zero q it is pxb_shrink_batch;
+ * flag_mask == 0 with an all-zero q is "ran OK within depth", which the benign
+ * schedule holds, so every such row shrinks to no faults.  Faults, neutralising,
+ * the settling, the rounds, the budget, the statuses, the signature, the
+ * in-place shrink in a scratch copy written back at the end, the nullable
+ * outputs, one stream synchronisation per launch and the independence of a
+ * row's outputs from its batch are pxb_shrink_batch's, unchanged.  One output
+ * more:
+ *   d_masks      uint32 (nullable): the coverage mask of the returned row's
+ *                accepted run; NOT_INPUT / TOO_MANY: the given row's mask as
+ *                pxb_cover gives it (0 when its status is not PXB_TRACE_OK),
+ *                beside d_results, which is the given row's as well.
+ * Scratch is pxb_shrink_batch's plus 4 B per row and, in the initial and prefix
+ * launches, 4 B per candidate.  PXB_E_INVAL, before any device call, for
+ * everything pxb_shrink_batch refuses except flag_mask & 0xFF == 0, and for a
+ * null pred, flag_mask & ~0xFF, a non-zero reserved word of pred or q, mask bits
+ * at or above PXB_COVER_CLASSES in q, a misaligned d_masks and
+ * PXB_CFG_TRACE_PRODUCTION.                                                   */
+typedef struct pxb_shrink_pred {   /* 32 B */
+  uint32_t flag_mask;               /* PXB_F_* bits; 0: no outcome condition       */
+  uint32_t max_launches;            /* >= 1                                        */
+  uint32_t reserved[2];             /* must be 0                                   */
+  pxb_cover_query q;                /* reserved must be 0                          */
+} pxb_shrink_pred;
+int pxb_shrink_cover_batch_device(const pxb_config* cfg, uint8_t* d_rows, uint64_t count, uint32_t depth,
+                                  const pxb_shrink_pred* pred,
+                                  uint32_t* d_status, uint32_t* d_n_faults, uint32_t* d_launches,
+                                  uint16_t* d_sent, pxb_result* d_results, uint64_t* d_signature,
+                                  uint32_t* d_masks, void* stream);
+/* pxb_shrink_cover_batch: HOST buffers, blocking, on the current device;
+ * PXB_E_NODEV without a GPU (checked after the validation above).  ids
+ * non-null: rows is output only, as pxb_shrink_batch.                         */
+int pxb_shrink_cover_batch(const pxb_config* cfg, const uint64_t* ids, uint8_t* rows, uint64_t count, uint32_t depth,
+                           const pxb_shrink_pred* pred,
+                           uint32_t* status, uint32_t* n_faults, uint32_t* launches,
+                           uint16_t* sent, pxb_result* results, uint64_t* signature, uint32_t* masks);
+
 /* ---- misc ----------------------------------------------------------------- */
 const char* pxb_strerror(int code);
 int         pxb_last_hip_error(void);
