@@ -243,6 +243,8 @@ __host__ __device__ __forceinline__ bool any_lane(bool p) {
 enum : uint32_t {
   EVP_END = 1u << 0, EVP_FIN = 1u << 1, EVP_RUN = 1u << 2, EVP_TICK_ENTER = 1u << 3, EVP_TICK_END = 1u << 4,
   EVP_ACC = 1u << 5, EVP_PROP = 1u << 6, EVP_COPY = 1u << 7, EVP_SEND1 = 1u << 8, EVP_BCAST = 1u << 9,
+  // an Execute broadcast; its restart's AskForTicket; an Execute at its acceptor's ticket (run or panic)
+  EVP_EXEC = 1u << 10, EVP_RESTART = 1u << 11, EVP_HIT = 1u << 12,
   // bail causes: ring slot still referenced, response FIFO full, response pool
   // empty, request FIFO full, log length, reply seq
   EVB_RING = 1u << 16, EVB_RFIFO = 1u << 17, EVB_POOL = 1u << 18, EVB_QFIFO = 1u << 19, EVB_LOG = 1u << 20,
@@ -412,8 +414,9 @@ struct EvLane : Src {
 #else
   static constexpr bool CARRY2 = false;
 #endif
-  // (a count only with CARRY2: a lane-mask bool is one scalar op to update)
-  typename std::conditional<CARRY2, uint32_t, bool>::type pqo;
+  // (a 0 / 1 word, a count only with CARRY2: as a bool it was re-made from a
+  // VGPR at the top of every iteration and put back at its end)
+  uint32_t pqo;
   uint32_t canon0;                    // canon on entering a step that carries one over (else canon - 1)
   pool_mask_t pfree;                  // free response-pool words
   uint32_t lflags, rounds, dval, dtick, execs, msgs, canon;   // (msgs: the replies; see msgs_sent)
@@ -591,7 +594,7 @@ struct EvLane : Src {
   // 48 canonical bytes per proposer with an input (SEMANTICS §8)
   __host__ __device__ __forceinline__ void enter(int32_t t) {
     s = t;
-    pqo = CARRY2 ? pq_len : (pq_len != 0u);          // (at most one, CARRY2 two: end_op)
+    pqo = pq_len;                                    // (at most one, CARRY2 two: end_op)
     if constexpr (!SP) canon0 = pqo ? canon : canon - 1u;   // (SP: see end_op)
     const uint32_t slot = (uint32_t)t & WM;
     uint32_t wq, wi;
@@ -772,10 +775,18 @@ struct EvLane : Src {
                                                      uint32_t x1, bool p1, uint32_t val) {
     rounds += ((p0 & (kind0 == ASK)) ? 1u : 0u) + (p1 ? 1u : 0u);
     const bool ex = p0 & (kind0 == EXECUTE);
-    execs += ex ? 1u : 0u;
-    const bool first = ex & (dval == 0u);             // the decided value: first Execute (Client.hs:178)
-    dval = first ? val : dval;
-    dtick = first ? x0 : dtick;
+    PXB_EV_PROBE(EVP_EXEC, ex);
+    PXB_EV_PROBE(EVP_RESTART, p1);
+    // The decision bookkeeping only where some lane of the wave broadcasts an
+    // Execute (config 4, tight layout: 42 % of wave-iterations, 0.9 % of lanes;
+    // tools/wave_model.cpp), not as compares and selects in every iteration
+    if (any_lane(ex)) {
+      opaque_barrier();
+      execs += ex ? 1u : 0u;
+      const bool first = ex & (dval == 0u);           // the decided value: first Execute (Client.hs:178)
+      dval = first ? val : dval;
+      dtick = first ? x0 : dtick;
+    }
     // (slot1 from slot0's register: LLVM otherwise extracted the field a second time)
     const uint32_t slot0 = CPK ? opaque(bslot_of(q)) : bslot_of(q), slot1 = (slot0 + 1u) & (S::BR - 1u);
     // a ring slot still referenced by a queued copy
@@ -834,7 +845,7 @@ struct EvLane : Src {
                                                      bool act = true) {
     const bool isR = rp.snd;                         // (only with act: acc_op)
     // the copy's bookkeeping (as in copy_send)
-    const uint32_t sb = (uint32_t)s - (pqo ? 1u : 0u);
+    const uint32_t sb = (uint32_t)s - (CARRY2 ? (pqo ? 1u : 0u) : pqo);
     const bool csnd = act & !isR & (pq_len != 0u);
     const uint32_t ce = pq & 31u;
     const uint32_t cp = ce >> 3, cslot = ce & 7u, ca = acur;
@@ -846,7 +857,7 @@ struct EvLane : Src {
       pq = wrap ? pq >> 5 : pq;
       pq_len -= wrap ? 1u : 0u;
       if constexpr (CARRY2) pqo -= (wrap & (pqo != 0u)) ? 1u : 0u;
-      else pqo = pqo & !wrap;
+      else pqo = wrap ? 0u : pqo;
       nsent_add(cp, ck, wrap ? 1u : 0u);
     }
     const bool snd = isR | csnd;
@@ -973,7 +984,7 @@ struct EvLane : Src {
   }
   __host__ __device__ __forceinline__ void copy_send(const EvParams& kp, bool act, const uint4& w) {
     // the broadcast's own step: s, or s - 1 for one carried over by end_op
-    const uint32_t sb = (uint32_t)s - (pqo ? 1u : 0u);
+    const uint32_t sb = (uint32_t)s - (CARRY2 ? (pqo ? 1u : 0u) : pqo);
     const uint32_t s4 = sb & 15u;
     const bool snd = act & (pq_len != 0u);
     PXB_EV_PROBE(EVP_COPY, snd);
@@ -987,7 +998,7 @@ struct EvLane : Src {
       pq = wrap ? pq >> 5 : pq;
       pq_len -= wrap ? 1u : 0u;
       if constexpr (CARRY2) pqo -= (wrap & (pqo != 0u)) ? 1u : 0u;
-      else pqo = pqo & !wrap;
+      else pqo = wrap ? 0u : pqo;
       nsent_add(cp, ck, wrap ? 1u : 0u);
     }
     // (w: the draw of copy_ctr() taken before this call)
@@ -1040,6 +1051,10 @@ struct EvLane : Src {
     // overlaps the acceptor op (config 4 +1.7 %, config 3 +0.7 %, config 5 +0.9 %);
     // the copy before the proposer op measured 1-3 % slower.
     Reply rp;
+    // The bail flag is this iteration's own: every driver leaves the instance
+    // on the first iteration that sets it, so it is false on entry and is not
+    // carried round the loop (init's bail, P above the shape's, is the refill's)
+    bailed = false;
     prop_op(kp, act);
     const uint2 c = copy_ctr();
     copy_send(kp, act, draw(c.x, c.y));
@@ -1125,70 +1140,83 @@ struct EvLane : Src {
     const bool grant = is_ask & !(t_max >= x);                // Server.hs:56
     const bool accept = is_prop & (x == t_max);                 // :66 (equality, not >=)
     const bool hit = is_exec & (t_max == x);                    // :75
-    const bool panic = hit & (val == 0u);                       // :76 (Q6)
+    [[maybe_unused]] const bool panic = hit & (val == 0u);      // :76 (Q6)
     const bool run = hit & (val != 0u);                         // :77-78
     const uint32_t rz = grant ? val : 0u;             // LG: the Round1OK's command (rp.z)
-    lflags |= panic ? (uint32_t)PXB_F_PANIC : 0u;
     PXB_EV_PROBE(EVP_RUN, run);
-    if (__builtin_expect(run, 0)) {                  // executed <>= [c]: log, digest, divergence
-      if (log_len >= A_LEN_MAX) bailed = true;
-      PXB_EV_PROBE(EVB_LOG, log_len >= A_LEN_MAX);
-      put(accd, a, fnv_u32(get(accd, a), code_of(val)));
-      if constexpr (LG) {                            // the canonical log's first LOG_TRACK positions (LDS)
-        // (straight-line: compare or append at position log_len, the halfword
-        // stored back when neither; a position past LOG_TRACK only flags.
-        // Log mode's Execute branch runs in 91 % of its wave-iterations, for
-        // 4 % of the lanes: nested exec-mask branches cost every one of them)
-        const bool trk = log_len < (uint32_t)PXB_LOG_TRACK;
-        const uint32_t li = trk ? log_len : (uint32_t)PXB_LOG_TRACK - 1u;
-        const bool seen = log_len < clog_len;
-        const bool app = trk & !seen;
-        uint32_t old;
-        if constexpr (S::CLP) {
-          // position li at bit 14 li of the packed words: a 64-bit window of
-          // words w and w + 1 (the last position ends at bit 32 of word CLW - 1,
-          // whose window is that word twice: stored high half first, low last)
-          const uint32_t b = mulc<14>(li), w = b >> 5, sh = b & 31u;
-          const uint32_t w1 = (w + 1u < (uint32_t)S::CLW) ? w + 1u : w;
-          const uint32_t lo = m.ld(S::CLOG + w), hi = m.ld(S::CLOG + w1);
-          const unsigned long long v = ((unsigned long long)hi << 32) | lo;
-          old = (uint32_t)(v >> sh) & 0x3FFFu;
-          const unsigned long long nv = app ? (v & ~(0x3FFFull << sh)) | ((unsigned long long)val << sh) : v;
-          m.st(S::CLOG + w1, (uint32_t)(nv >> 32));
-          m.st(S::CLOG + w, (uint32_t)nv);
-        } else {
-          const uint32_t cw = S::CLOG + (li >> 1), ch = li & 1u;
-          old = m.ld16h(cw, ch);
-          m.st16h(cw, ch, app ? val : old);
-        }
-        lflags |= (trk & seen & (old != val)) ? (uint32_t)PXB_F_LOG_DIVERGENCE : 0u;
-        lflags |= trk ? 0u : (uint32_t)PXB_F_LOG_TRUNC;
-        clog_len += app ? 1u : 0u;
+    PXB_EV_PROBE(EVP_HIT, hit);
+    // What an Execute at the acceptor's own ticket does to its word -- the log
+    // entry (run) or the dead bit (panic, Q6) -- is selected inside the branch
+    // that the log, digest and divergence check already took (config 4, tight
+    // layout: 23 % of wave-iterations, 0.4 % of lanes, tools/wave_model.cpp),
+    // not among the candidates of every iteration.  (Log mode takes its branch
+    // in 91 % of its wave-iterations and keeps it one level deep: run only,
+    // the panic's select after it.)
+    uint32_t Ah = A, Vh = V;
+    if (__builtin_expect(LG ? run : hit, 0)) {
+      if constexpr (LG) {
+        Ah = A & ~0xFFF000u;
+        Vh = (V & ~0x3FFFu) + (1u << A_LEN);
       } else {
-        if (log_len < clog_len) {
-          if (((uint32_t)(clog >> (2u * log_len)) & 3u) != val) lflags |= PXB_F_LOG_DIVERGENCE;
-        } else {
-          clog |= (unsigned long long)val << (2u * log_len);
-          clog_len += 1u;
-        }
+        Ah = run ? (A & 0xFC000FFFu) + (1u << 27) : A | (1u << A_DEAD);
       }
-      log_len += 1u;
+      if (LG || run) {                               // executed <>= [c]: log, digest, divergence
+        if (log_len >= A_LEN_MAX) bailed = true;
+        PXB_EV_PROBE(EVB_LOG, log_len >= A_LEN_MAX);
+        put(accd, a, fnv_u32(get(accd, a), code_of(val)));
+        if constexpr (LG) {                            // the canonical log's first LOG_TRACK positions (LDS)
+          // (straight-line: compare or append at position log_len, the halfword
+          // stored back when neither; a position past LOG_TRACK only flags.
+          // Log mode's Execute branch runs in 91 % of its wave-iterations, for
+          // 4 % of the lanes: nested exec-mask branches cost every one of them)
+          const bool trk = log_len < (uint32_t)PXB_LOG_TRACK;
+          const uint32_t li = trk ? log_len : (uint32_t)PXB_LOG_TRACK - 1u;
+          const bool seen = log_len < clog_len;
+          const bool app = trk & !seen;
+          uint32_t old;
+          if constexpr (S::CLP) {
+            // position li at bit 14 li of the packed words: a 64-bit window of
+            // words w and w + 1 (the last position ends at bit 32 of word CLW - 1,
+            // whose window is that word twice: stored high half first, low last)
+            const uint32_t b = mulc<14>(li), w = b >> 5, sh = b & 31u;
+            const uint32_t w1 = (w + 1u < (uint32_t)S::CLW) ? w + 1u : w;
+            const uint32_t lo = m.ld(S::CLOG + w), hi = m.ld(S::CLOG + w1);
+            const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+            old = (uint32_t)(v >> sh) & 0x3FFFu;
+            const unsigned long long nv = app ? (v & ~(0x3FFFull << sh)) | ((unsigned long long)val << sh) : v;
+            m.st(S::CLOG + w1, (uint32_t)(nv >> 32));
+            m.st(S::CLOG + w, (uint32_t)nv);
+          } else {
+            const uint32_t cw = S::CLOG + (li >> 1), ch = li & 1u;
+            old = m.ld16h(cw, ch);
+            m.st16h(cw, ch, app ? val : old);
+          }
+          lflags |= (trk & seen & (old != val)) ? (uint32_t)PXB_F_LOG_DIVERGENCE : 0u;
+          lflags |= trk ? 0u : (uint32_t)PXB_F_LOG_TRUNC;
+          clog_len += app ? 1u : 0u;
+        } else {
+          if (log_len < clog_len) {
+            if (((uint32_t)(clog >> (2u * log_len)) & 3u) != val) lflags |= PXB_F_LOG_DIVERGENCE;
+          } else {
+            clog |= (unsigned long long)val << (2u * log_len);
+            clog_len += 1u;
+          }
+        }
+        log_len += 1u;
+      }
     }
+    if constexpr (LG) Ah = panic ? A | (1u << A_DEAD) : Ah;
     // (a lane without a live request rebuilds its old word unchanged)
     uint32_t pw;                                     // the reply's response word
     if constexpr (LG) {
       // (as below: accw = t_max | t_store << 12 | dead << 24, accv = the
       // stored command | log length << 14; the Round1OK's command goes in rp.z)
       const uint32_t c_gr = (A & ~0xFFFu) | x, c_ac = (A & ~0xFFF000u) | (x << 12);
-      const uint32_t c_rn = A & ~0xFFF000u, c_pn = A | (1u << A_DEAD);
-      uint32_t An = panic ? c_pn : A;
-      An = run ? c_rn : An;
-      An = accept ? c_ac : An;
+      uint32_t An = accept ? c_ac : Ah;
       An = grant ? c_gr : An;
       put(accw, a, An);
-      const uint32_t v_ac = (V & ~0x3FFFu) | z, v_rn = (V & ~0x3FFFu) + (1u << A_LEN);
-      uint32_t Vn = run ? v_rn : V;
-      Vn = accept ? v_ac : Vn;
+      const uint32_t v_ac = (V & ~0x3FFFu) | z;
+      const uint32_t Vn = accept ? v_ac : Vh;
       put(accv, a, Vn);
       const uint32_t p_gr = x | (A & 0xFFF000u) | (R1OK << 30), p_hv = (A & 0xFFFu) | (HAVE << 30);
       constexpr uint32_t p_ac = R2S << 30;
@@ -1196,15 +1224,13 @@ struct EvLane : Src {
       pw = grant ? p_gr : pw;
     } else {
       // whole-word updates (candidates, then selects of plain values): grant
-      // sets t_max; accept sets t_store and val; Execute clears them and
-      // appends (log length + 1; a 32nd entry bailed above); panic sets dead.
+      // sets t_max; accept sets t_store and val; an Execute's word (Ah: t_store
+      // and val cleared, log length + 1, or the dead bit of a panic) comes from
+      // its branch above.
       // A Round1OK carries (x, t_store, val), which sit in the reply's fields
       // at their acceptor-word offsets.
       const uint32_t c_gr = (A & ~0xFFFu) | x, c_ac = (A & 0xFC000FFFu) | (x << 12) | (z << 24);
-      const uint32_t c_rn = (A & 0xFC000FFFu) + (1u << 27), c_pn = A | (1u << 26);
-      uint32_t An = panic ? c_pn : A;
-      An = run ? c_rn : An;
-      An = accept ? c_ac : An;
+      uint32_t An = accept ? c_ac : Ah;
       An = grant ? c_gr : An;
       put(accw, a, An);
       const uint32_t p_gr = x | (A & 0x03FFF000u) | (R1OK << 30), p_hv = (A & 0xFFFu) | (HAVE << 30);
@@ -1373,7 +1399,10 @@ struct EvLane : Src {
       // the next step with a due message or a Tick (skews of absent proposers are 0)
       const uint32_t s1 = (uint32_t)s + 1u;
       const uint32_t rot = (occ >> (s1 & WM)) & ((1u << W) - 1u);   // (occupied slots from s1 on)
-      uint32_t nx = ((occ != 0u) & (pq_len == 0u)) ? s1 + ctz32(rot) : (pq_len ? s1 : 0xFFFFu);
+      // (SP: no Tick after init, and a lane with nothing queued and an empty
+      // wheel is quiet and never reads nx: s1, or the first occupied slot's step)
+      uint32_t nx = SP ? s1 + (pq_len ? 0u : (uint32_t)__builtin_ctz(rot | (1u << W)))
+                       : ((occ != 0u) & (pq_len == 0u)) ? s1 + ctz32(rot) : (pq_len ? s1 : 0xFFFFu);
       PXB_EV_PROBE(EVP_TICK_END, s < last_tick);
       if (!SP && any_lane(s < last_tick)) {           // (a later Tick: first steps only)
         opaque_barrier();
@@ -1411,6 +1440,11 @@ struct EvLane : Src {
 #pragma unroll
     for (int p = 0; p < PM; ++p)
       f |= (!capped && (uint32_t)p < P && p_state(p) != IDLE) ? (uint32_t)PXB_F_STUCK : 0u;
+    // (a panic is what sets an acceptor's dead bit, and nothing clears it)
+    uint32_t dead = 0u;
+#pragma unroll
+    for (int a = 0; a < N; ++a) dead |= accw[a];
+    f |= ((dead >> A_DEAD) & 1u) ? (uint32_t)PXB_F_PANIC : 0u;
     canon += 16u + 4u * (uint32_t)N;
     o.res[0] = dval ? code_of(dval) : 0u;
     o.res[1] = dval ? dtick : 0u;

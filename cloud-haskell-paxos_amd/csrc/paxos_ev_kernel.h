@@ -321,7 +321,12 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
     };
     // (iterations until some lane ends or bails: the inner loop's back edge
     // is the one ballot)
+    // (done and the bail flag are each iteration's own -- the loop ends on the
+    // first one that sets either -- so neither is carried round it for the
+    // lanes the branch below masks off)
     do {
+      done = false;
+      L.bailed = false;
       if (L.mode != M_IDLE) done = L.step(kp.p, o, true, fin);
     } while (__builtin_amdgcn_ballot_w64(done | L.bailed) == 0ull);
     if (__builtin_expect(L.bailed, 0)) {      // beyond this kernel's capacities: re-run by the general kernel

@@ -40,8 +40,9 @@ struct HostMem {
   void orw(uint32_t i, uint32_t v) const { w[i] |= v; }
 };
 
-constexpr int NB = 10;
-const char* names[NB] = {"END", "FIN", "RUN", "TICK_ENTER", "TICK_END", "ACC", "PROP", "COPY", "SEND1", "BCAST"};
+constexpr int NB = 13;
+const char* names[NB] = {"END", "FIN", "RUN", "TICK_ENTER", "TICK_END", "ACC", "PROP", "COPY", "SEND1", "BCAST",
+                         "EXEC", "RESTART", "HIT"};
 
 // (ids: run only these instances, as a second-stage kernel over another's
 // hand-offs; bailed_out: the ids this shape hands on)
