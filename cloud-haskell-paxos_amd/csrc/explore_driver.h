@@ -1,16 +1,30 @@
-// explore_list.h — what follows the candidate kernel of an exploration, shared
-// by pxb_explore (paxos_explore.hip) and pxb_explore_cover
-// (paxos_explore_cover.hip) over the candidates' flag bytes: the minimal kernel
-// with the per-(parent, radius) counts and the status, hipCUB's exclusive sum
-// over the tiles, the cursor kernel and the scatter kernel, the call's scratch
-// and the rules of a space.  The kernels live in an unnamed namespace: each of
-// the two units has its own.  Included only where entry points are (hipCUB).
+// explore_driver.h — the explorer's driver (include/paxos_batch.h,
+// docs/SEMANTICS.md §12, §15): what pxb_explore (paxos_explore.hip) and
+// pxb_explore_cover (paxos_explore_cover.hip) share around their candidate
+// kernels, as shrink_driver.h is the shrinkers'.
+//   What follows the candidate kernel, over the candidates' flag bytes: the
+//     minimal kernel with the per-(parent, radius) counts and the status,
+//     hipCUB's exclusive sum over the tiles, the cursor kernel and the scatter
+//     kernel.
+//   explore_validate: the argument rules of every exploring call (a family's
+//     own rules, and the kernel of the shape, stay with the family).
+//   explore_device: the device form after validation.  Parameterised by the
+//     candidate launch: the kernel, and its parameter struct, of which the
+//     family has set its own fields and the driver fills those every such
+//     struct has under the same names; and by two hooks that may queue kernels
+//     in front of and behind the candidate launch.
+//   explore_staged: the chunked host-buffer form around a device form given as
+//     a callable, with one optional per-parent column of the family's.
+// The kernels live in an unnamed namespace: each of the two units has its own.
+// Included only where entry points are (hipCUB).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/paxos_batch.h"
 #include "explore_core.h"
 #include "host_util.h"
+
+extern "C" uint64_t explore_chunk_hook(void);   // paxos_batch.hip: PXB_EXPLORE_CHUNK
 
 namespace pxx {
 namespace {
@@ -134,6 +148,30 @@ inline int validate_space_of(const pxb_config* cfg, uint32_t depth, uint32_t sit
   return e->T ? PXB_OK : PXB_E_INVAL;
 }
 
+// an exploring call's arguments, whichever the family: device pointers in a
+// device form, host pointers in a host-buffer form
+struct ExpArgs {
+  const pxb_config* cfg;
+  const uint8_t* rows;
+  uint64_t count;
+  uint32_t depth;
+  uint64_t first_parent;
+  uint64_t* ids;
+  uint64_t capacity;
+  uint64_t* n_matches;
+  uint32_t* counts;                 // (nullable, as status)
+  uint32_t* status;
+};
+// the argument rules every exploring call shares; Space: pxb_explore_space or
+// pxb_explore_cover_space (what flag_mask may be is the family's rule)
+template <class Space>
+inline int explore_validate(const ExpArgs& a, const Space* sp, ExploreSpace* e) {
+  if (!sp) return PXB_E_INVAL;
+  if (int rc = validate_space_of(a.cfg, a.depth, sp->site_depth, sp->radius, e)) return rc;
+  if ((a.count && !a.rows) || a.count > MAX_COUNT || !a.n_matches || (a.capacity && !a.ids)) return PXB_E_INVAL;
+  return (sp->flags & ~PXB_EXPLORE_MINIMAL) ? PXB_E_INVAL : PXB_OK;
+}
+
 // the scratch of a device call over `total` candidates, from the stream-ordered
 // pool: list base | flag bytes | tile counts | tile offsets | scan
 struct ExpScratch {
@@ -183,6 +221,106 @@ inline hipError_t explore_list(const ExpList& l, const ExpScratch& s, uint64_t f
     err = hipGetLastError();
   }
   return err;
+}
+
+inline hipError_t explore_no_hook(hipStream_t) { return hipSuccess; }
+
+// The device form over validated arguments `a` on stream st: one call's bound
+// and the pointers' alignment (a family tests its own column's first), then
+// the counts zeroed | before(st) | fn(c) over the candidates | after(st) | the
+// minimal bits, counts, status and list, in this order on st.  `c`: the
+// candidate kernel's parameters with the family's own fields set; p, e, rows,
+// stride, total, depth, site_depth, flag_mask and bytes are set here.
+template <class Params, class Space, class Before, class After>
+int explore_device(const ExpArgs& a, const Space* sp, const ExploreSpace& e, hipStream_t st, void (*fn)(Params),
+                   Params& c, const Before& before, const After& after) {
+  if (a.count * e.T > MAX_CALL) return PXB_E_INVAL;                     // (count <= 2^30, T <= 2^30)
+  if (((uintptr_t)a.rows & 7u) || ((uintptr_t)a.ids & 7u) || ((uintptr_t)a.n_matches & 7u) ||
+      ((uintptr_t)a.counts & 3u) || ((uintptr_t)a.status & 3u))
+    return PXB_E_INVAL;
+  int dev = 0;
+  if (int rc = current_device(&dev)) return rc;
+  if (a.count == 0) return PXB_OK;
+
+  const uint64_t total = a.count * e.T;
+  ExpScratch x;
+  if (int rc = explore_scratch(dev, total, st, &x)) return rc;
+
+  c.p = make_params(a.cfg);
+  c.p.first_instance = 0;
+  c.e = e;
+  c.rows = a.rows;
+  c.stride = script_stride(a.cfg->n_proposers, a.cfg->n_acceptors, a.depth);
+  c.total = total;
+  c.depth = a.depth;
+  c.site_depth = sp->site_depth;
+  c.flag_mask = sp->flag_mask;
+  c.bytes = x.bytes;
+  ExpList l{};
+  l.e = e;
+  l.rows = a.rows;
+  l.stride = c.stride;
+  l.total = total;
+  l.P = a.cfg->n_proposers;
+  l.sel = (sp->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
+  l.bytes = x.bytes;
+  l.tcount = x.tcount;
+  l.counts = a.counts;
+  l.status = a.status;
+
+  hipError_t err = hipSuccess;
+  do {
+    if (a.counts && (err = hipMemsetAsync(a.counts, 0, (size_t)(a.count * 12u * 4u), st)) != hipSuccess) break;
+    if ((err = before(st)) != hipSuccess) break;
+    hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63u) / 64u)), dim3(64), 0, st, c);
+    if ((err = hipGetLastError()) != hipSuccess) break;
+    if ((err = after(st)) != hipSuccess) break;
+    err = explore_list(l, x, a.first_parent * e.T, a.ids, a.capacity, a.n_matches, st);
+  } while (0);
+  const hipError_t f = hipFreeAsync(x.buf, st);   // (stream-ordered: after the launches above)
+  if (err == hipSuccess) err = f;
+  return (err == hipSuccess) ? PXB_OK : hip_fail(err);
+}
+
+// The host-buffer form over validated host arguments `h`, around a device form:
+// whole parents, at most PXB_EXPLORE_CHUNK candidates a chunk (and at least one
+// parent); call(d, d_extra) runs the device form on the null stream over the
+// chunk's device arguments `d`.  `extra` (nullable), of extra_elem bytes a
+// parent (0: the family has none): the family's own per-parent output column.
+// An output the caller did not ask for reaches the device form as null.
+template <class Call>
+int explore_staged(const ExpArgs& h, const ExploreSpace& e, void* extra, uint64_t extra_elem, const Call& call) {
+  if (device_count() == 0) return PXB_E_NODEV;
+  *h.n_matches = 0;
+  if (h.count == 0) return PXB_OK;
+  const uint64_t chunk = explore_chunk_hook();
+  const uint64_t per = chunk / e.T ? chunk / e.T : 1u, m_max = per < h.count ? per : h.count;
+  const uint64_t stride = script_stride(h.cfg->n_proposers, h.cfg->n_acceptors, h.depth);
+  const uint64_t cap = h.capacity < h.count * e.T ? h.capacity : h.count * e.T;
+  pxb::StagePlan plan;                            // rows (one chunk) | cursor | ids | counts | [extra] | status
+  const pxb::StageRegion r_rows = plan.add(stride, m_max), r_n = plan.add(sizeof(uint64_t), 1);
+  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_cnt = plan.add(12u * sizeof(uint32_t), h.count);
+  const pxb::StageRegion r_x = plan.add(extra_elem, h.count), r_st = plan.add(sizeof(uint32_t), h.count);
+  Staging S(plan);
+  S.zero(r_n);
+  uint32_t* const d_cnt = S.ptr<uint32_t>(r_cnt, h.counts);
+  char* const d_x = S.ptr<char>(r_x, extra);
+  uint32_t* const d_st = S.ptr<uint32_t>(r_st, h.status);
+  for (uint64_t a = 0; a < h.count && S.ok(); a += m_max) {
+    const uint64_t m = h.count - a < m_max ? h.count - a : m_max;
+    S.up(r_rows, h.rows + a * stride, m);
+    const ExpArgs d{h.cfg, S.ptr<uint8_t>(r_rows), m, h.depth, a, S.ptr<uint64_t>(r_ids), cap, S.ptr<uint64_t>(r_n),
+                    d_cnt ? d_cnt + a * 12u : nullptr, d_st ? d_st + a : nullptr};
+    if (S.ok()) S.note(call(d, d_x ? d_x + a * extra_elem : nullptr));
+    // (the next chunk's rows overwrite these: wait for the kernels that read them)
+    if (S.ok()) S.note(hipStreamSynchronize(nullptr));
+  }
+  S.down(r_n, h.n_matches, 1);
+  if (S.ok()) S.down(r_ids, h.ids, *h.n_matches < cap ? *h.n_matches : cap);
+  S.down(r_cnt, h.counts, h.count);
+  S.down(r_x, extra, h.count);
+  S.down(r_st, h.status, h.count);
+  return S.finish();
 }
 
 }  // namespace

@@ -116,20 +116,12 @@ __global__ __launch_bounds__(64) void paxos_cover_kernel(CovParams k) {
 }
 
 typedef void (*cov_ptr)(CovParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none)
-template <int PM>
-cov_ptr cov_pick(const pxb_config* cfg);
-template <> cov_ptr cov_pick<1>(const pxb_config* cfg);
-template <> cov_ptr cov_pick<2>(const pxb_config* cfg);
-template <> cov_ptr cov_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct CovKernel {
-  template <int N, int W, bool LG>
-  cov_ptr shape() const { return paxos_cover_kernel<PM, N, W, LG>; }
+struct CovFamily {                  // (lane_shapes.h)
+  typedef cov_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_cover_kernel<PM, N, W, LG>; }
 };
-template <>
-cov_ptr cov_pick<PXB_COV_P>(const pxb_config* cfg) { return lane_shape(cfg, CovKernel<PXB_COV_P>{}, (cov_ptr) nullptr); }
+PXB_LANE_UNIT(CovFamily, PXB_COV_P)
 
 }  // namespace ev
 }  // namespace pxb
@@ -226,16 +218,10 @@ __global__ __launch_bounds__(256) void cover_append_kernel(const uint32_t* sel, 
 }
 __global__ void cover_count_kernel(pxb_cover_summary* s, const uint32_t* n_sel) { s->n_matches += *n_sel; }
 
-struct CovPick {
-  const pxb_config* cfg;
-  template <int PM>
-  cov_ptr proposers() const { return cov_pick<PM>(cfg); }
-};
-
 // the config rules every form shares
 static int validate_cfg(const pxb_config* cfg, cov_ptr* fn) {
   if (!cfg || !trace_config_ok(cfg) || (cfg->flags & PXB_CFG_TRACE_PRODUCTION)) return PXB_E_INVAL;
-  *fn = lane_proposers(cfg, CovPick{cfg}, (cov_ptr) nullptr);
+  *fn = lane_kernel<CovFamily>(cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 static int validate_rows(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth, cov_ptr* fn) {

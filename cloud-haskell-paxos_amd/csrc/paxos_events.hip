@@ -85,20 +85,12 @@ __global__ __launch_bounds__(64) void paxos_events_kernel(EvtParams k) {
 }
 
 typedef void (*evt_ptr)(EvtParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none)
-template <int PM>
-evt_ptr evt_pick(const pxb_config* cfg);
-template <> evt_ptr evt_pick<1>(const pxb_config* cfg);
-template <> evt_ptr evt_pick<2>(const pxb_config* cfg);
-template <> evt_ptr evt_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct EvtKernel {
-  template <int N, int W, bool LG>
-  evt_ptr shape() const { return paxos_events_kernel<PM, N, W, LG>; }
+struct EvtFamily {                  // (lane_shapes.h)
+  typedef evt_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_events_kernel<PM, N, W, LG>; }
 };
-template <>
-evt_ptr evt_pick<PXB_EVT_P>(const pxb_config* cfg) { return lane_shape(cfg, EvtKernel<PXB_EVT_P>{}, (evt_ptr) nullptr); }
+PXB_LANE_UNIT(EvtFamily, PXB_EVT_P)
 
 }  // namespace ev
 }  // namespace pxb
@@ -121,12 +113,6 @@ __global__ __launch_bounds__(256) void paxos_events_place_kernel(const pxb_trace
     event_place(staging, staged, offsets, count, t, out, capacity);
 }
 
-struct EvtPick {
-  const pxb_config* cfg;
-  template <int PM>
-  evt_ptr proposers() const { return evt_pick<PM>(cfg); }
-};
-
 // the argument rules both forms share
 static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth, const pxb_trace_sel* sel,
                     const void* events, uint64_t capacity, const void* offsets, evt_ptr* fn) {
@@ -134,7 +120,7 @@ static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uin
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
   if (!offsets || (sel && (sel->reserved != 0u || sel->tail != 0u)) || (!events && capacity)) return PXB_E_INVAL;
   if (cfg->flags & PXB_CFG_TRACE_PRODUCTION) return PXB_E_INVAL;
-  *fn = lane_proposers(cfg, EvtPick{cfg}, (evt_ptr) nullptr);
+  *fn = lane_kernel<EvtFamily>(cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 

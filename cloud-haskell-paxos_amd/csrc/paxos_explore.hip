@@ -20,8 +20,8 @@
 //     the flag bytes: ascending g from the caller's cursor, below `capacity`.
 // Everything is sized from count x T: the device form never synchronises.  No
 // block waits for another; plain vector stores only.  All but the candidate
-// kernel live in explore_list.h, which pxb_explore_cover
-// (paxos_explore_cover.hip) shares.
+// kernel, and the host side of both calls, live in explore_driver.h, which
+// pxb_explore_cover (paxos_explore_cover.hip) shares.
 //
 // Built as three units by proposer count (-DPXB_EXP_P=1|2|3) so that the slow
 // device compiles overlap; the unit of P = 1 also holds the other kernels and
@@ -91,55 +91,27 @@ __global__ __launch_bounds__(64) void paxos_explore_kernel(ExpParams k) {
 }
 
 typedef void (*exp_ptr)(ExpParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none);
-// each unit specialises it for its own proposer count
-template <int PM>
-exp_ptr exp_pick(const pxb_config* cfg);
-template <> exp_ptr exp_pick<1>(const pxb_config* cfg);
-template <> exp_ptr exp_pick<2>(const pxb_config* cfg);
-template <> exp_ptr exp_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct ExpKernel {
-  template <int N, int W, bool LG>
-  exp_ptr shape() const { return paxos_explore_kernel<PM, N, W, LG>; }
+struct ExpFamily {                  // (lane_shapes.h)
+  typedef exp_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_explore_kernel<PM, N, W, LG>; }
 };
-template <>
-exp_ptr exp_pick<PXB_EXP_P>(const pxb_config* cfg) { return lane_shape(cfg, ExpKernel<PXB_EXP_P>{}, (exp_ptr) nullptr); }
+PXB_LANE_UNIT(ExpFamily, PXB_EXP_P)
 
 }  // namespace ev
 }  // namespace pxb
 
 #if PXB_EXP_P == 1
-#include "explore_list.h"
-
-extern "C" uint64_t explore_chunk_hook(void);   // paxos_batch.hip: PXB_EXPLORE_CHUNK
+#include "explore_driver.h"
 
 namespace pxx {
-using namespace pxb::ev;
-using namespace pxb::host;
 
-struct ExpPick {
-  const pxb_config* cfg;
-  template <int PM>
-  exp_ptr proposers() const { return exp_pick<PM>(cfg); }
-};
-static int pick(const pxb_config* cfg, exp_ptr* fn) {
-  *fn = lane_proposers(cfg, ExpPick{cfg}, (exp_ptr) nullptr);
+// explore_driver.h's rules and pxb_explore's own: an outcome condition; *fn: the shape's kernel
+static int validate(const ExpArgs& a, const pxb_explore_space* sp, ExploreSpace* e, exp_ptr* fn) {
+  if (int rc = explore_validate(a, sp, e)) return rc;
+  if ((sp->flag_mask & 0xFFu) == 0u) return PXB_E_INVAL;
+  *fn = lane_kernel<ExpFamily>(a.cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
-}
-static int validate_space(const pxb_config* cfg, uint32_t depth, const pxb_explore_space* sp, ExploreSpace* e) {
-  if (!sp) return PXB_E_INVAL;
-  return validate_space_of(cfg, depth, sp->site_depth, sp->radius, e);
-}
-// the argument rules both calls share
-static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,
-                    const pxb_explore_space* sp, const void* ids, uint64_t capacity, const void* n_matches,
-                    ExploreSpace* e, exp_ptr* fn) {
-  if (int rc = validate_space(cfg, depth, sp, e)) return rc;
-  if ((count && !rows) || count > MAX_COUNT || !n_matches || (capacity && !ids)) return PXB_E_INVAL;
-  if ((sp->flag_mask & 0xFFu) == 0u || (sp->flags & ~PXB_EXPLORE_MINIMAL) != 0u) return PXB_E_INVAL;
-  return pick(cfg, fn);
 }
 
 }  // namespace pxx
@@ -155,7 +127,8 @@ int pxb_explore_row(const pxb_config* cfg, uint32_t depth, const pxb_explore_spa
                     uint64_t c, uint8_t* out_row) {
   using namespace pxx;
   ExploreSpace e;
-  if (int rc = validate_space(cfg, depth, space, &e)) return rc;
+  if (!space) return PXB_E_INVAL;
+  if (int rc = validate_space_of(cfg, depth, space->site_depth, space->radius, &e)) return rc;
   if (!parent || !out_row || c >= e.T) return PXB_E_INVAL;
   const uint32_t N = cfg->n_acceptors;
   const ExploreByte x = explore_byte(e, explore_unrank(e, c), parent, N, space->site_depth, depth);
@@ -171,96 +144,26 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
                        const pxb_explore_space* space, uint64_t first_parent, uint64_t* d_ids, uint64_t capacity,
                        uint64_t* d_n_matches, uint32_t* d_counts, uint32_t* d_status, void* stream) {
   using namespace pxx;
+  const ExpArgs a{cfg, d_rows, count, depth, first_parent, d_ids, capacity, d_n_matches, d_counts, d_status};
   ExploreSpace e;
   exp_ptr fn = nullptr;
-  if (int rc = validate(cfg, d_rows, count, depth, space, d_ids, capacity, d_n_matches, &e, &fn)) return rc;
-  if (count * e.T > MAX_CALL) return PXB_E_INVAL;                       // (count <= 2^30, T <= 2^30)
-  if (((uintptr_t)d_rows & 7u) || ((uintptr_t)d_ids & 7u) || ((uintptr_t)d_n_matches & 7u) ||
-      ((uintptr_t)d_counts & 3u) || ((uintptr_t)d_status & 3u))
-    return PXB_E_INVAL;
-  const hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (count == 0) return PXB_OK;
-
-  const uint64_t total = count * e.T;
-  ExpScratch x;
-  if (int rc = explore_scratch(dev, total, st, &x)) return rc;
-  uint8_t* const bytes = x.bytes;
-
+  if (int rc = validate(a, space, &e, &fn)) return rc;
   ExpParams c{};
-  c.p = make_params(cfg);
-  c.p.first_instance = 0;
-  c.e = e;
-  c.rows = d_rows;
-  c.stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
-  c.total = total;
-  c.depth = depth;
-  c.site_depth = space->site_depth;
-  c.flag_mask = space->flag_mask;
-  c.bytes = bytes;
-  ExpList l{};
-  l.e = e;
-  l.rows = d_rows;
-  l.stride = c.stride;
-  l.total = total;
-  l.P = cfg->n_proposers;
-  l.sel = (space->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
-  l.bytes = bytes;
-  l.tcount = x.tcount;
-  l.counts = d_counts;
-  l.status = d_status;
-
-  hipError_t err = hipSuccess;
-  do {
-    if (d_counts && (err = hipMemsetAsync(d_counts, 0, (size_t)(count * 12u * 4u), st)) != hipSuccess) break;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63u) / 64u)), dim3(64), 0, st, c);
-    if ((err = hipGetLastError()) != hipSuccess) break;
-    err = explore_list(l, x, first_parent * e.T, d_ids, capacity, d_n_matches, st);
-  } while (0);
-  const hipError_t f = hipFreeAsync(x.buf, st);   // (stream-ordered: after the launches above)
-  if (err == hipSuccess) err = f;
-  return (err == hipSuccess) ? PXB_OK : hip_fail(err);
+  return explore_device(a, space, e, (hipStream_t)stream, fn, c, explore_no_hook, explore_no_hook);
 }
 
 int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
                 const pxb_explore_space* space, uint64_t* ids, uint64_t capacity, uint64_t* n_matches,
                 uint32_t* counts, uint32_t* status) {
   using namespace pxx;
+  const ExpArgs h{cfg, rows, count, depth, 0, ids, capacity, n_matches, counts, status};
   ExploreSpace e;
   exp_ptr fn = nullptr;
-  if (int rc = validate(cfg, rows, count, depth, space, ids, capacity, n_matches, &e, &fn)) return rc;
-  if (device_count() == 0) return PXB_E_NODEV;
-  *n_matches = 0;
-  if (count == 0) return PXB_OK;
-  // whole parents, at most PXB_EXPLORE_CHUNK candidates a chunk (and at least one parent)
-  const uint64_t chunk = explore_chunk_hook();
-  const uint64_t per = chunk / e.T ? chunk / e.T : 1u, m_max = per < count ? per : count;
-  const uint64_t stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
-  const uint64_t cap = capacity < count * e.T ? capacity : count * e.T;
-  pxb::StagePlan plan;                            // rows (one chunk) | cursor | ids | counts | status
-  const pxb::StageRegion r_rows = plan.add(stride, m_max), r_n = plan.add(sizeof(uint64_t), 1);
-  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_cnt = plan.add(12u * sizeof(uint32_t), count);
-  const pxb::StageRegion r_st = plan.add(sizeof(uint32_t), count);
-  Staging S(plan);
-  S.zero(r_n);
-  uint32_t* const d_cnt = S.ptr<uint32_t>(r_cnt, counts);
-  uint32_t* const d_st = S.ptr<uint32_t>(r_st, status);
-  for (uint64_t a = 0; a < count && S.ok(); a += m_max) {
-    const uint64_t m = count - a < m_max ? count - a : m_max;
-    S.up(r_rows, rows + a * stride, m);
-    if (S.ok())
-      S.note(pxb_explore_device(cfg, S.ptr<uint8_t>(r_rows), m, depth, space, a, S.ptr<uint64_t>(r_ids), cap,
-                                S.ptr<uint64_t>(r_n), d_cnt ? d_cnt + a * 12u : nullptr, d_st ? d_st + a : nullptr,
-                                nullptr));
-    // (the next chunk's rows overwrite these: wait for the kernels that read them)
-    if (S.ok()) S.note(hipStreamSynchronize(nullptr));
-  }
-  S.down(r_n, n_matches, 1);
-  if (S.ok()) S.down(r_ids, ids, *n_matches < cap ? *n_matches : cap);
-  S.down(r_cnt, counts, count);
-  S.down(r_st, status, count);
-  return S.finish();
+  if (int rc = validate(h, space, &e, &fn)) return rc;
+  return explore_staged(h, e, nullptr, 0, [&](const ExpArgs& d, void*) {
+    return pxb_explore_device(cfg, d.rows, d.count, depth, space, d.first_parent, d.ids, d.capacity, d.n_matches,
+                              d.counts, d.status, nullptr);
+  });
 }
 
 }  // extern "C"

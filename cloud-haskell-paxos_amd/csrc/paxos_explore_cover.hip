@@ -17,8 +17,8 @@
 // parent c ascends with the lane).  Integer adds and minima only: the records
 // do not depend on the order the waves end in.  An init kernel in front sets
 // the records, a finishing kernel behind gives union_mask.  The list is
-// pxb_explore's (explore_list.h) over the flag bytes.  No block waits for
-// another; plain vector stores only.
+// pxb_explore's (explore_driver.h, with the host side of both calls) over the
+// flag bytes.  No block waits for another; plain vector stores only.
 //
 // Built as three units by proposer count (-DPXB_EXC_P=1|2|3); the unit of P = 1
 // also holds the other kernels and the entry points.
@@ -115,28 +115,18 @@ __global__ __launch_bounds__(64) void paxos_explore_cover_kernel(ExcParams k) {
 }
 
 typedef void (*exc_ptr)(ExcParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none)
-template <int PM>
-exc_ptr exc_pick(const pxb_config* cfg);
-template <> exc_ptr exc_pick<1>(const pxb_config* cfg);
-template <> exc_ptr exc_pick<2>(const pxb_config* cfg);
-template <> exc_ptr exc_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct ExcKernel {
-  template <int N, int W, bool LG>
-  exc_ptr shape() const { return paxos_explore_cover_kernel<PM, N, W, LG>; }
+struct ExcFamily {                  // (lane_shapes.h)
+  typedef exc_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_explore_cover_kernel<PM, N, W, LG>; }
 };
-template <>
-exc_ptr exc_pick<PXB_EXC_P>(const pxb_config* cfg) { return lane_shape(cfg, ExcKernel<PXB_EXC_P>{}, (exc_ptr) nullptr); }
+PXB_LANE_UNIT(ExcFamily, PXB_EXC_P)
 
 }  // namespace ev
 }  // namespace pxb
 
 #if PXB_EXC_P == 1
-#include "explore_list.h"
-
-extern "C" uint64_t explore_chunk_hook(void);   // paxos_batch.hip: PXB_EXPLORE_CHUNK
+#include "explore_driver.h"
 
 namespace pxx {
 
@@ -161,23 +151,14 @@ __global__ __launch_bounds__(32) void reach_finish_kernel(pxb_explore_reach* rea
   if (b == 0u) o->union_mask = (uint32_t)bal;
 }
 
-struct ExcPick {
-  const pxb_config* cfg;
-  template <int PM>
-  exc_ptr proposers() const { return exc_pick<PM>(cfg); }
-};
-
-// the argument rules both calls share
-static int validate(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,
-                    const pxb_explore_cover_space* sp, const void* ids, uint64_t capacity, const void* n_matches,
-                    ExploreSpace* e, exc_ptr* fn) {
-  if (!sp) return PXB_E_INVAL;
-  if (int rc = validate_space_of(cfg, depth, sp->site_depth, sp->radius, e)) return rc;
-  if ((count && !rows) || count > MAX_COUNT || !n_matches || (capacity && !ids)) return PXB_E_INVAL;
-  if ((sp->flags & ~PXB_EXPLORE_MINIMAL) != 0u || sp->q.reserved != 0u) return PXB_E_INVAL;
-  if ((sp->flag_mask != 0u && (sp->flag_mask & 0xFFu) == 0u) || (cfg->flags & PXB_CFG_TRACE_PRODUCTION))
-    return PXB_E_INVAL;
-  *fn = lane_proposers(cfg, ExcPick{cfg}, (exc_ptr) nullptr);
+// explore_driver.h's rules and pxb_explore_cover's own: no outcome condition, or
+// one over the outcome bits; no reserved word; no production draws (the event
+// lanes have none); *fn: the shape's kernel
+static int validate(const ExpArgs& a, const pxb_explore_cover_space* sp, ExploreSpace* e, exc_ptr* fn) {
+  if (int rc = explore_validate(a, sp, e)) return rc;
+  if ((sp->flag_mask != 0u && (sp->flag_mask & 0xFFu) == 0u) || sp->q.reserved != 0u) return PXB_E_INVAL;
+  if (a.cfg->flags & PXB_CFG_TRACE_PRODUCTION) return PXB_E_INVAL;
+  *fn = lane_kernel<ExcFamily>(a.cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 
@@ -190,109 +171,43 @@ int pxb_explore_cover_device(const pxb_config* cfg, const uint8_t* d_rows, uint6
                              uint64_t capacity, uint64_t* d_n_matches, uint32_t* d_counts, pxb_explore_reach* d_reach,
                              uint32_t* d_status, void* stream) {
   using namespace pxx;
+  const ExpArgs a{cfg, d_rows, count, depth, first_parent, d_ids, capacity, d_n_matches, d_counts, d_status};
   ExploreSpace e;
   exc_ptr fn = nullptr;
-  if (int rc = validate(cfg, d_rows, count, depth, space, d_ids, capacity, d_n_matches, &e, &fn)) return rc;
-  if (count * e.T > MAX_CALL) return PXB_E_INVAL;                       // (count <= 2^30, T <= 2^30)
-  if (((uintptr_t)d_rows & 7u) || ((uintptr_t)d_ids & 7u) || ((uintptr_t)d_n_matches & 7u) ||
-      ((uintptr_t)d_counts & 3u) || ((uintptr_t)d_reach & 7u) || ((uintptr_t)d_status & 3u))
-    return PXB_E_INVAL;
-  const hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (count == 0) return PXB_OK;
-
-  const uint64_t total = count * e.T;
-  ExpScratch x;
-  if (int rc = explore_scratch(dev, total, st, &x)) return rc;
-
+  if (int rc = validate(a, space, &e, &fn)) return rc;
+  if ((uintptr_t)d_reach & 7u) return PXB_E_INVAL;
   ExcParams c{};
-  c.p = make_params(cfg);
-  c.p.first_instance = 0;
-  c.e = e;
-  c.rows = d_rows;
-  c.stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
-  c.total = total;
-  c.depth = depth;
-  c.site_depth = space->site_depth;
-  c.flag_mask = space->flag_mask;
   c.q = space->q;
-  c.bytes = x.bytes;
   c.reach = d_reach;
-  ExpList l{};
-  l.e = e;
-  l.rows = d_rows;
-  l.stride = c.stride;
-  l.total = total;
-  l.P = cfg->n_proposers;
-  l.sel = (space->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
-  l.bytes = x.bytes;
-  l.tcount = x.tcount;
-  l.counts = d_counts;
-  l.status = d_status;
-
-  hipError_t err = hipSuccess;
-  do {
-    if (d_counts && (err = hipMemsetAsync(d_counts, 0, (size_t)(count * 12u * 4u), st)) != hipSuccess) break;
-    if (d_reach) {
-      const uint64_t n_words = count * REACH_WORDS;
-      hipLaunchKernelGGL(reach_init_kernel, dim3((unsigned)((n_words + 255u) / 256u)), dim3(256), 0, st,
-                         reinterpret_cast<uint32_t*>(d_reach), n_words);
-      if ((err = hipGetLastError()) != hipSuccess) break;
-    }
-    hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63u) / 64u)), dim3(64), 0, st, c);
-    if ((err = hipGetLastError()) != hipSuccess) break;
-    if (d_reach) {
-      hipLaunchKernelGGL(reach_finish_kernel, dim3((unsigned)count), dim3(32), 0, st, d_reach);
-      if ((err = hipGetLastError()) != hipSuccess) break;
-    }
-    err = explore_list(l, x, first_parent * e.T, d_ids, capacity, d_n_matches, st);
-  } while (0);
-  const hipError_t f = hipFreeAsync(x.buf, st);   // (stream-ordered: after the launches above)
-  if (err == hipSuccess) err = f;
-  return (err == hipSuccess) ? PXB_OK : hip_fail(err);
+  // the records set in front of the candidates, union_mask behind them
+  const auto init = [&](hipStream_t st) {
+    if (!d_reach) return hipSuccess;
+    const uint64_t n_words = count * REACH_WORDS;
+    hipLaunchKernelGGL(reach_init_kernel, dim3((unsigned)((n_words + 255u) / 256u)), dim3(256), 0, st,
+                       reinterpret_cast<uint32_t*>(d_reach), n_words);
+    return hipGetLastError();
+  };
+  const auto finish = [&](hipStream_t st) {
+    if (!d_reach) return hipSuccess;
+    hipLaunchKernelGGL(reach_finish_kernel, dim3((unsigned)count), dim3(32), 0, st, d_reach);
+    return hipGetLastError();
+  };
+  return explore_device(a, space, e, (hipStream_t)stream, fn, c, init, finish);
 }
 
 int pxb_explore_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
                       const pxb_explore_cover_space* space, uint64_t* ids, uint64_t capacity, uint64_t* n_matches,
                       uint32_t* counts, pxb_explore_reach* reach, uint32_t* status) {
   using namespace pxx;
+  const ExpArgs h{cfg, rows, count, depth, 0, ids, capacity, n_matches, counts, status};
   ExploreSpace e;
   exc_ptr fn = nullptr;
-  if (int rc = validate(cfg, rows, count, depth, space, ids, capacity, n_matches, &e, &fn)) return rc;
-  if (device_count() == 0) return PXB_E_NODEV;
-  *n_matches = 0;
-  if (count == 0) return PXB_OK;
-  // whole parents, at most PXB_EXPLORE_CHUNK candidates a chunk (and at least one parent)
-  const uint64_t chunk = explore_chunk_hook();
-  const uint64_t per = chunk / e.T ? chunk / e.T : 1u, m_max = per < count ? per : count;
-  const uint64_t stride = script_stride(cfg->n_proposers, cfg->n_acceptors, depth);
-  const uint64_t cap = capacity < count * e.T ? capacity : count * e.T;
-  pxb::StagePlan plan;                            // rows (one chunk) | cursor | ids | counts | reach | status
-  const pxb::StageRegion r_rows = plan.add(stride, m_max), r_n = plan.add(sizeof(uint64_t), 1);
-  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_cnt = plan.add(12u * sizeof(uint32_t), count);
-  const pxb::StageRegion r_rch = plan.add(sizeof(pxb_explore_reach), count), r_st = plan.add(sizeof(uint32_t), count);
-  Staging S(plan);
-  S.zero(r_n);
-  uint32_t* const d_cnt = S.ptr<uint32_t>(r_cnt, counts);
-  pxb_explore_reach* const d_rch = S.ptr<pxb_explore_reach>(r_rch, reach);
-  uint32_t* const d_st = S.ptr<uint32_t>(r_st, status);
-  for (uint64_t a = 0; a < count && S.ok(); a += m_max) {
-    const uint64_t m = count - a < m_max ? count - a : m_max;
-    S.up(r_rows, rows + a * stride, m);
-    if (S.ok())
-      S.note(pxb_explore_cover_device(cfg, S.ptr<uint8_t>(r_rows), m, depth, space, a, S.ptr<uint64_t>(r_ids), cap,
-                                      S.ptr<uint64_t>(r_n), d_cnt ? d_cnt + a * 12u : nullptr,
-                                      d_rch ? d_rch + a : nullptr, d_st ? d_st + a : nullptr, nullptr));
-    // (the next chunk's rows overwrite these: wait for the kernels that read them)
-    if (S.ok()) S.note(hipStreamSynchronize(nullptr));
-  }
-  S.down(r_n, n_matches, 1);
-  if (S.ok()) S.down(r_ids, ids, *n_matches < cap ? *n_matches : cap);
-  S.down(r_cnt, counts, count);
-  S.down(r_rch, reach, count);
-  S.down(r_st, status, count);
-  return S.finish();
+  if (int rc = validate(h, space, &e, &fn)) return rc;
+  return explore_staged(h, e, reach, sizeof(pxb_explore_reach), [&](const ExpArgs& d, void* d_reach) {
+    return pxb_explore_cover_device(cfg, d.rows, d.count, depth, space, d.first_parent, d.ids, d.capacity,
+                                    d.n_matches, d.counts, static_cast<pxb_explore_reach*>(d_reach), d.status,
+                                    nullptr);
+  });
 }
 
 }  // extern "C"

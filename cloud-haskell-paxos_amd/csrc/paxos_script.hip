@@ -113,21 +113,12 @@ __global__ __launch_bounds__(64) void paxos_script_kernel(ScrParams k) {
 }
 
 typedef void (*scr_ptr)(ScrParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none);
-// each unit specialises it for its own proposer count
-template <int PM>
-scr_ptr scr_pick(const pxb_config* cfg);
-template <> scr_ptr scr_pick<1>(const pxb_config* cfg);
-template <> scr_ptr scr_pick<2>(const pxb_config* cfg);
-template <> scr_ptr scr_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct ScrKernel {
-  template <int N, int W, bool LG>
-  scr_ptr shape() const { return paxos_script_kernel<PM, N, W, LG>; }
+struct ScrFamily {                  // (lane_shapes.h)
+  typedef scr_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_script_kernel<PM, N, W, LG>; }
 };
-template <>
-scr_ptr scr_pick<PXB_SCR_P>(const pxb_config* cfg) { return lane_shape(cfg, ScrKernel<PXB_SCR_P>{}, (scr_ptr) nullptr); }
+PXB_LANE_UNIT(ScrFamily, PXB_SCR_P)
 
 }  // namespace ev
 }  // namespace pxb
@@ -163,13 +154,8 @@ static int validate_cfg(const pxb_config* cfg, const void* rows, uint64_t count,
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
   return PXB_OK;
 }
-struct ScrPick {
-  const pxb_config* cfg;
-  template <int PM>
-  scr_ptr proposers() const { return scr_pick<PM>(cfg); }
-};
 static int pick(const pxb_config* cfg, scr_ptr* fn) {
-  *fn = lane_proposers(cfg, ScrPick{cfg}, (scr_ptr) nullptr);
+  *fn = lane_kernel<ScrFamily>(cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 static int validate_trace(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,

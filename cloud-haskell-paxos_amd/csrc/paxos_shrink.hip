@@ -69,21 +69,12 @@ __global__ __launch_bounds__(64) void paxos_shrink_kernel(ShrParams k) {
 }
 
 typedef void (*shr_ptr)(ShrParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none);
-// each unit specialises it for its own proposer count
-template <int PM>
-shr_ptr shr_pick(const pxb_config* cfg);
-template <> shr_ptr shr_pick<1>(const pxb_config* cfg);
-template <> shr_ptr shr_pick<2>(const pxb_config* cfg);
-template <> shr_ptr shr_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct ShrKernel {
-  template <int N, int W, bool LG>
-  shr_ptr shape() const { return paxos_shrink_kernel<PM, N, W, LG>; }
+struct ShrFamily {                  // (lane_shapes.h)
+  typedef shr_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_shrink_kernel<PM, N, W, LG>; }
 };
-template <>
-shr_ptr shr_pick<PXB_SHR_P>(const pxb_config* cfg) { return lane_shape(cfg, ShrKernel<PXB_SHR_P>{}, (shr_ptr) nullptr); }
+PXB_LANE_UNIT(ShrFamily, PXB_SHR_P)
 
 }  // namespace ev
 }  // namespace pxb
@@ -93,13 +84,8 @@ shr_ptr shr_pick<PXB_SHR_P>(const pxb_config* cfg) { return lane_shape(cfg, ShrK
 
 namespace pxsh {
 
-struct ShrPick {
-  const pxb_config* cfg;
-  template <int PM>
-  shr_ptr proposers() const { return shr_pick<PM>(cfg); }
-};
 static int pick(const pxb_config* cfg, shr_ptr* fn) {
-  *fn = lane_proposers(cfg, ShrPick{cfg}, (shr_ptr) nullptr);
+  *fn = lane_kernel<ShrFamily>(cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 // the argument rules both calls share

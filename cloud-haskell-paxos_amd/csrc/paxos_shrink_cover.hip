@@ -67,20 +67,12 @@ __global__ __launch_bounds__(64) void paxos_shrink_cover_kernel(ShcParams k) {
 }
 
 typedef void (*shc_ptr)(ShcParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none)
-template <int PM>
-shc_ptr shc_pick(const pxb_config* cfg);
-template <> shc_ptr shc_pick<1>(const pxb_config* cfg);
-template <> shc_ptr shc_pick<2>(const pxb_config* cfg);
-template <> shc_ptr shc_pick<3>(const pxb_config* cfg);
-
-template <int PM>
-struct ShcKernel {
-  template <int N, int W, bool LG>
-  shc_ptr shape() const { return paxos_shrink_cover_kernel<PM, N, W, LG>; }
+struct ShcFamily {                  // (lane_shapes.h)
+  typedef shc_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_shrink_cover_kernel<PM, N, W, LG>; }
 };
-template <>
-shc_ptr shc_pick<PXB_SHC_P>(const pxb_config* cfg) { return lane_shape(cfg, ShcKernel<PXB_SHC_P>{}, (shc_ptr) nullptr); }
+PXB_LANE_UNIT(ShcFamily, PXB_SHC_P)
 
 }  // namespace ev
 }  // namespace pxb
@@ -90,11 +82,6 @@ shc_ptr shc_pick<PXB_SHC_P>(const pxb_config* cfg) { return lane_shape(cfg, ShcK
 
 namespace pxsh {
 
-struct ShcPick {
-  const pxb_config* cfg;
-  template <int PM>
-  shc_ptr proposers() const { return shc_pick<PM>(cfg); }
-};
 // the argument rules both calls share
 static int validate_cover(const pxb_config* cfg, const void* rows, uint64_t count, uint32_t depth,
                           const pxb_shrink_pred* pred, shc_ptr* fn) {
@@ -104,7 +91,7 @@ static int validate_cover(const pxb_config* cfg, const void* rows, uint64_t coun
   if ((pred->flag_mask & ~0xFFu) || pred->reserved[0] || pred->reserved[1] || pred->q.reserved) return PXB_E_INVAL;
   if ((pred->q.all_mask | pred->q.any_mask | pred->q.none_mask) & ~CLASSES) return PXB_E_INVAL;
   if (cfg->flags & PXB_CFG_TRACE_PRODUCTION) return PXB_E_INVAL;
-  *fn = lane_proposers(cfg, ShcPick{cfg}, (shc_ptr) nullptr);
+  *fn = lane_kernel<ShcFamily>(cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 

@@ -60,24 +60,15 @@ __global__ __launch_bounds__(64) void paxos_trace_batch_kernel(TrbParams k) {
 }
 
 typedef void (*trb_ptr)(TrbParams);
-// the kernel of a config's shape among the unit's of PM proposers (null: none);
-// each unit specialises it for its own proposer count
-template <int PM>
-trb_ptr trb_pick(const pxb_config* cfg);
-template <> trb_ptr trb_pick<1>(const pxb_config* cfg);
-template <> trb_ptr trb_pick<2>(const pxb_config* cfg);
-template <> trb_ptr trb_pick<3>(const pxb_config* cfg);
-
-template <int PM, bool EARLY>
-struct TrbKernel {
-  template <int N, int W, bool LG>
-  trb_ptr shape() const { return paxos_trace_batch_kernel<PM, N, W, EARLY, LG>; }
+// two families (lane_shapes.h): the production draws' kernels and the others
+template <bool EARLY>
+struct TrbFamily {
+  typedef trb_ptr ptr;
+  template <int PM, int N, int W, bool LG>
+  static ptr kernel() { return paxos_trace_batch_kernel<PM, N, W, EARLY, LG>; }
 };
-template <>
-trb_ptr trb_pick<PXB_TRB_P>(const pxb_config* cfg) {
-  return (cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? lane_shape(cfg, TrbKernel<PXB_TRB_P, true>{}, (trb_ptr) nullptr)
-                                                 : lane_shape(cfg, TrbKernel<PXB_TRB_P, false>{}, (trb_ptr) nullptr);
-}
+PXB_LANE_UNIT(TrbFamily<true>, PXB_TRB_P)
+PXB_LANE_UNIT(TrbFamily<false>, PXB_TRB_P)
 
 }  // namespace ev
 }  // namespace pxb
@@ -96,12 +87,6 @@ struct Kept {
 };
 typedef hipcub::TransformInputIterator<uint64_t, Kept, const uint32_t*> kept_iter;
 
-struct TrbPick {
-  const pxb_config* cfg;
-  template <int PM>
-  trb_ptr proposers() const { return trb_pick<PM>(cfg); }
-};
-
 // the argument rules of both forms; *fn: the shape's kernel
 int validate(const pxb_config* cfg, const void* ids, uint64_t count, const pxb_trace_sel* sel, const void* records,
              uint64_t capacity, const void* offsets, trb_ptr* fn) {
@@ -109,7 +94,7 @@ int validate(const pxb_config* cfg, const void* ids, uint64_t count, const pxb_t
   if (sel && sel->reserved != 0u) return PXB_E_INVAL;
   if (!records && capacity) return PXB_E_INVAL;
   if (!trace_config_ok(cfg)) return PXB_E_INVAL;
-  *fn = lane_proposers(cfg, TrbPick{cfg}, (trb_ptr) nullptr);
+  *fn = (cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? lane_kernel<TrbFamily<true>>(cfg) : lane_kernel<TrbFamily<false>>(cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
 }
 

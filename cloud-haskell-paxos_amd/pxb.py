@@ -1779,6 +1779,35 @@ def explore_rows(cfg: Config, parents, depth: int, site_depth: int, radius: int,
     return rows
 
 
+def _explore_two_call(call, nm, capacity):
+    """The listing protocol of the exploring host forms: call(ids pointer,
+    capacity) runs the form, which leaves the match count in `nm`.  capacity
+    None: a sizing call first, and no second call when nothing matches.
+    Returns the listed ids."""
+    import numpy as np
+    if capacity is None:
+        call(None, 0)
+        capacity = nm.value
+        if capacity == 0:
+            return np.zeros(0, dtype=np.uint64)
+    ids = np.zeros(capacity, dtype=np.uint64)
+    call(_ptr(ids) if capacity else None, capacity)
+    return ids[:min(nm.value, capacity)]
+
+
+def _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacity, d_counts, d_status):
+    """The checks the exploring device forms share."""
+    if d_n_matches is None:
+        raise ValueError("d_n_matches is required")
+    if capacity and d_ids is None:
+        raise ValueError("d_ids is required when capacity > 0")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_n_matches", d_n_matches, 1, 8)
+    _check_buf("d_ids", d_ids, capacity, 8)
+    _check_buf("d_counts", d_counts, 12 * count, 4)
+    _check_buf("d_status", d_status, count, 4)
+
+
 def explore(cfg: Config, parents, depth: int, site_depth: int, radius: int, flag_mask: int, minimal: bool = True,
             capacity=None):
     """pxb_explore: every schedule within `radius` changed sites of each parent
@@ -1800,14 +1829,8 @@ def explore(cfg: Config, parents, depth: int, site_depth: int, radius: int, flag
     nm = C.c_uint64(0)
     head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sp))
     tail = (C.byref(nm), _ptr(counts) if n else None, _ptr(status) if n else None)
-    if capacity is None:
-        check(lib.pxb_explore(*head, None, 0, *tail))
-        capacity = nm.value
-        if capacity == 0:
-            return np.zeros(0, dtype=np.uint64), 0, counts, status
-    ids = np.zeros(capacity, dtype=np.uint64)
-    check(lib.pxb_explore(*head, _ptr(ids) if capacity else None, capacity, *tail))
-    return ids[:min(nm.value, capacity)], nm.value, counts, status
+    ids = _explore_two_call(lambda p, cap: check(lib.pxb_explore(*head, p, cap, *tail)), nm, capacity)
+    return ids, nm.value, counts, status
 
 
 def explore_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int, radius: int, flag_mask: int,
@@ -1818,15 +1841,7 @@ def explore_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int,
     write cursor, which has the call's full count added; d_ids int64 (capacity,)
     takes (first_parent + i) * T + c, ascending; d_counts int32 (count, 4, 3)
     and d_status int32 (count,) optional.  Sizes and dtypes are checked here."""
-    if d_n_matches is None:
-        raise ValueError("d_n_matches is required")
-    if capacity and d_ids is None:
-        raise ValueError("d_ids is required when capacity > 0")
-    _check_script_call(cfg, d_rows, count, depth)
-    _check_buf("d_n_matches", d_n_matches, 1, 8)
-    _check_buf("d_ids", d_ids, capacity, 8)
-    _check_buf("d_counts", d_counts, 12 * count, 4)
-    _check_buf("d_status", d_status, count, 4)
+    _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacity, d_counts, d_status)
     c = cfg.to_c(0, 1)
     sp = pxb_explore_space(site_depth, radius, flag_mask, EXPLORE_MINIMAL if minimal else 0)
     s = C.c_void_p(stream) if stream else None
@@ -1942,13 +1957,8 @@ def explore_cover(cfg: Config, parents, depth: int, site_depth: int, radius: int
     nm = C.c_uint64(0)
     head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sp))
     tail = (C.byref(nm), _ptr(counts) if n else None, _ptr(reach) if n else None, _ptr(status) if n else None)
-    if capacity is None:
-        check(lib.pxb_explore_cover(*head, None, 0, *tail))
-        capacity = nm.value
-    ids = np.zeros(capacity, dtype=np.uint64)
-    if capacity:
-        check(lib.pxb_explore_cover(*head, _ptr(ids), capacity, *tail))
-    return ids[:min(nm.value, capacity)], nm.value, counts, [ExploreReach.from_record(r) for r in reach], status
+    ids = _explore_two_call(lambda p, cap: check(lib.pxb_explore_cover(*head, p, cap, *tail)), nm, capacity)
+    return ids, nm.value, counts, [ExploreReach.from_record(r) for r in reach], status
 
 
 def explore_cover_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int, radius: int, d_n_matches,
@@ -1959,15 +1969,7 @@ def explore_cover_device(cfg: Config, d_rows, count: int, depth: int, site_depth
     synchronisation: the buffers of explore_device, and d_reach uint8 (count *
     648,) (8-byte aligned; after a synchronise, d_reach.cpu().numpy().view(
     reach_dtype()) gives the records).  Sizes and dtypes are checked here."""
-    if d_n_matches is None:
-        raise ValueError("d_n_matches is required")
-    if capacity and d_ids is None:
-        raise ValueError("d_ids is required when capacity > 0")
-    _check_script_call(cfg, d_rows, count, depth)
-    _check_buf("d_n_matches", d_n_matches, 1, 8)
-    _check_buf("d_ids", d_ids, capacity, 8)
-    _check_buf("d_counts", d_counts, 12 * count, 4)
-    _check_buf("d_status", d_status, count, 4)
+    _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacity, d_counts, d_status)
     if d_reach is not None:
         _check_bytes("d_reach", d_reach, EXPLORE_REACH_BYTES * count)
     c = cfg.to_c(0, 1)

@@ -24,7 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "native", "explore_host.cpp")
 OUT = os.path.join(HERE, "native", "_build", "libexplore_host.so")
-DEPS = [SRC, os.path.join(HERE, "native", "host_lane.h")] + [
+DEPS = [SRC, os.path.join(HERE, "native", "host_lane.h"), os.path.join(HERE, "native", "explore_host.h")] + [
     os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
     for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h",
               "lane_shapes.h", "script_core.h", "script_lane.h", "shrink_core.h", "explore_core.h")] + [

@@ -76,18 +76,12 @@ int dispatch(const Args& a) {
   return -1;
 }
 #else
-template <int PM>
-struct RunShape {
+struct Run {
   const Args& a;
-  template <int N, int W, bool LG>
-  int shape() const { return run_shape<PM, N, W, LG>(a); }
+  template <int PM, int N, int W, bool LG>
+  int run() const { return run_shape<PM, N, W, LG>(a); }
 };
-struct RunProposers {
-  const Args& a;
-  template <int PM>
-  int proposers() const { return lane_shape(a.cfg, RunShape<PM>{a}, -1); }
-};
-int dispatch(const Args& a) { return lane_proposers(a.cfg, RunProposers{a}, -1); }
+int dispatch(const Args& a) { return host_lane_shape(a.cfg, Run{a}, -1); }
 #endif
 
 }  // namespace

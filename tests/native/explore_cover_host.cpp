@@ -18,6 +18,7 @@
 #include "../../cloud-haskell-paxos_amd/csrc/explore_cover_core.h"
 #include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
 #include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
+#include "explore_host.h"
 #include "host_lane.h"
 
 using namespace pxb;
@@ -78,18 +79,12 @@ int dispatch(const Cand& a) {
 }
 #else
 // (the shapes of lane_shapes.h; -1: none)
-template <int PM>
-struct RunShape {
+struct Run {
   const Cand& a;
-  template <int N, int W, bool LG>
-  int shape() const { return run_shape<PM, N, W, LG>(a); }
+  template <int PM, int N, int W, bool LG>
+  int run() const { return run_shape<PM, N, W, LG>(a); }
 };
-struct RunProposers {
-  const Cand& a;
-  template <int PM>
-  int proposers() const { return lane_shape(a.cfg, RunShape<PM>{a}, -1); }
-};
-int dispatch(const Cand& a) { return lane_proposers(a.cfg, RunProposers{a}, -1); }
+int dispatch(const Cand& a) { return host_lane_shape(a.cfg, Run{a}, -1); }
 #endif
 
 }  // namespace
@@ -112,6 +107,7 @@ extern "C" int explore_cover_host_run(const pxb_config* cfg, const uint8_t* rows
   const uint64_t stride = script_stride(P, N, depth);
   const uint32_t sel = (sp->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
   uint64_t pos = *n_matches;
+  const ExploreHostOut out{first_parent, ids, capacity, &pos, counts, status, bytes};
   std::vector<uint8_t> f((size_t)e.T);
   std::vector<uint32_t> m((size_t)e.T);
   for (uint64_t i = 0; i < count; ++i) {
@@ -120,30 +116,22 @@ extern "C" int explore_cover_host_run(const pxb_config* cfg, const uint8_t* rows
       if (int rc = dispatch(Cand{cfg, &e, row, depth, sp->site_depth, (uint32_t)c, sp->flag_mask, &sp->q,
                                  &f[(size_t)c], &m[(size_t)c]}))
         return rc;
-    uint32_t cnt[12] = {0u};
+    explore_host_parent(e, P, row, i, sel, f.data(), out);
+    // the reach record: the masks folded by radius and class
     pxb_explore_reach r;
     memset(&r, 0, sizeof r);
     for (int b = 0; b < 32; ++b) r.first[b] = 0xFFFFFFFFu;
     r.parent_mask = m[0];
     for (uint64_t c = 0; c < e.T; ++c) {
-      const ExploreCand k = explore_unrank(e, c);
-      if ((f[(size_t)c] & EXP_HELD) && explore_is_minimal(e, k, f.data())) f[(size_t)c] |= (uint8_t)EXP_MINIMAL;
-      for (uint32_t b = 0; b < 3u; ++b) cnt[k.r * 3u + b] += (f[(size_t)c] >> b) & 1u;
+      const uint32_t rad = explore_unrank(e, c).r;
       for (uint32_t b = 0; b < (uint32_t)PXB_COVER_CLASSES; ++b)
         if ((m[(size_t)c] >> b) & 1u) {
-          r.count[k.r][b] += 1u;
+          r.count[rad][b] += 1u;
           if ((uint32_t)c < r.first[b]) r.first[b] = (uint32_t)c;
           r.union_mask |= 1u << b;
         }
-      if (f[(size_t)c] & sel) {
-        if (pos < capacity) ids[pos] = (first_parent + i) * e.T + c;
-        ++pos;
-      }
     }
-    if (counts) memcpy(counts + i * 12u, cnt, sizeof(cnt));
     if (reach) memcpy(reinterpret_cast<unsigned char*>(reach) + i * sizeof r, &r, sizeof r);
-    if (status) status[i] = explore_parent_bad(row, P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
-    if (bytes) memcpy(bytes + i * e.T, f.data(), (size_t)e.T);
     if (masks) memcpy(masks + i * e.T, m.data(), (size_t)e.T * 4u);
   }
   *n_matches = pos;

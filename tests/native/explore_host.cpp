@@ -16,6 +16,7 @@
 #include "../../cloud-haskell-paxos_amd/csrc/explore_core.h"
 #include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
 #include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
+#include "explore_host.h"
 #include "host_lane.h"
 
 using namespace pxb;
@@ -67,18 +68,12 @@ int dispatch(const Cand& a) {
 }
 #else
 // (the shapes of lane_shapes.h; -1: none)
-template <int PM>
-struct RunShape {
+struct Run {
   const Cand& a;
-  template <int N, int W, bool LG>
-  int shape() const { return run_shape<PM, N, W, LG>(a); }
+  template <int PM, int N, int W, bool LG>
+  int run() const { return run_shape<PM, N, W, LG>(a); }
 };
-struct RunProposers {
-  const Cand& a;
-  template <int PM>
-  int proposers() const { return lane_shape(a.cfg, RunShape<PM>{a}, -1); }
-};
-int dispatch(const Cand& a) { return lane_proposers(a.cfg, RunProposers{a}, -1); }
+int dispatch(const Cand& a) { return host_lane_shape(a.cfg, Run{a}, -1); }
 #endif
 
 }  // namespace
@@ -133,25 +128,14 @@ int explore_host_run(const pxb_config* cfg, const uint8_t* rows, uint64_t count,
   const uint64_t stride = script_stride(P, N, depth);
   const uint32_t sel = (sp->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
   uint64_t pos = *n_matches;
+  const ExploreHostOut out{first_parent, ids, capacity, &pos, counts, status, bytes};
   std::vector<uint8_t> f((size_t)e.T);
   for (uint64_t i = 0; i < count; ++i) {
     const uint8_t* const row = rows + i * stride;
     for (uint64_t c = 0; c < e.T; ++c)
       if (int rc = dispatch(Cand{cfg, &e, row, depth, sp->site_depth, (uint32_t)c, sp->flag_mask, &f[(size_t)c]}))
         return rc;
-    uint32_t cnt[12] = {0u};
-    for (uint64_t c = 0; c < e.T; ++c) {
-      const ExploreCand k = explore_unrank(e, c);
-      if ((f[(size_t)c] & EXP_HELD) && explore_is_minimal(e, k, f.data())) f[(size_t)c] |= (uint8_t)EXP_MINIMAL;
-      for (uint32_t b = 0; b < 3u; ++b) cnt[k.r * 3u + b] += (f[(size_t)c] >> b) & 1u;
-      if (f[(size_t)c] & sel) {
-        if (pos < capacity) ids[pos] = (first_parent + i) * e.T + c;
-        ++pos;
-      }
-    }
-    if (counts) memcpy(counts + i * 12u, cnt, sizeof(cnt));
-    if (status) status[i] = explore_parent_bad(row, P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
-    if (bytes) memcpy(bytes + i * e.T, f.data(), (size_t)e.T);
+    explore_host_parent(e, P, row, i, sel, f.data(), out);
   }
   *n_matches = pos;
   return 0;

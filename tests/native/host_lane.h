@@ -1,10 +1,12 @@
-// host_lane.h — TEST ONLY: what the host builds of the lane jobs (trace_host.cpp,
-// script_host.cpp, shrink_host.cpp, explore_host.cpp) share: one lane's words
-// behind a checked accessor, and the guarded loop that stands where the kernels
-// have the wave's (script_run).  Around the loop trace_host.cpp calls the
-// kernel's own TrbParams::begin / finish and shrink_host.cpp the kernel's own
-// ShrParams::begin, over host pointers (host_run); script_host.cpp and
-// explore_host.cpp spell their lane's text out, as their kernels do.
+// host_lane.h — TEST ONLY: what the host builds of the lane jobs ({trace,
+// script, shrink, explore, events, cover, explore_cover, shrink_cover}_host.cpp)
+// share: one lane's words behind a checked accessor, the guarded loop that
+// stands where the kernels have the wave's (script_run), and the run of a
+// functor at a config's shape (host_lane_shape: the mirror of lane_shapes.h's
+// lane_kernel).  Around the loop trace_host.cpp calls the kernel's own
+// TrbParams::begin / finish and shrink_host.cpp the kernel's own
+// ShrParams::begin, over host pointers (host_run); the others spell their
+// lane's text out, as their kernels do.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -12,6 +14,7 @@
 
 #include <vector>
 
+#include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
 #include "../../cloud-haskell-paxos_amd/csrc/paxos_trace_core.h"
 
 #define PXB_HCHK(c)                                                                                       \
@@ -58,6 +61,26 @@ struct HostLane {
     L.set_keys(p);
   }
 };
+
+// f.run<PM, N, W, LG>() at the config's shape (lane_shapes.h), or `none`
+template <class F, class R, int PM>
+struct HostLaneShape {
+  const F& f;
+  template <int N, int W, bool LG>
+  R shape() const { return f.template run<PM, N, W, LG>(); }
+};
+template <class F, class R>
+struct HostLaneProposers {
+  const pxb_config* cfg;
+  const F& f;
+  R none;
+  template <int PM>
+  R proposers() const { return pxb::ev::lane_shape(cfg, HostLaneShape<F, R, PM>{f}, none); }
+};
+template <class F, class R>
+R host_lane_shape(const pxb_config* cfg, const F& f, R none) {
+  return pxb::ev::lane_proposers(cfg, HostLaneProposers<F, R>{cfg, f, none}, none);
+}
 
 // Job g as its kernel runs it up to k.finish, which the caller calls: k.begin
 // (*started: its answer), then the started lane to its end.  False: the lane did

@@ -68,18 +68,12 @@ int dispatch(const Cand& a) {
 }
 #else
 // (the shapes of lane_shapes.h; -1: none)
-template <int PM>
-struct RunShape {
+struct Run {
   const Cand& a;
-  template <int N, int W, bool LG>
-  int shape() const { return run_shape<PM, N, W, LG>(a); }
+  template <int PM, int N, int W, bool LG>
+  int run() const { return run_shape<PM, N, W, LG>(a); }
 };
-struct RunProposers {
-  const Cand& a;
-  template <int PM>
-  int proposers() const { return lane_shape(a.cfg, RunShape<PM>{a}, -1); }
-};
-int dispatch(const Cand& a) { return lane_proposers(a.cfg, RunProposers{a}, -1); }
+int dispatch(const Cand& a) { return host_lane_shape(a.cfg, Run{a}, -1); }
 #endif
 
 // One launch of the candidate kernel over one parent: its candidates 0 .. n - 1.

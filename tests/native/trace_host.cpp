@@ -78,22 +78,14 @@ int dispatch(const Args& a) {
 }
 #else
 // (the shapes of lane_shapes.h; -1: none)
-template <int PM, bool E>
-struct RunShape {
+struct Run {
   const Args& a;
-  template <int N, int W, bool LG>
-  int shape() const { return run_shape<PM, N, W, E, LG>(a); }
+  template <int PM, int N, int W, bool LG>
+  int run() const {
+    return (a.cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? run_shape<PM, N, W, true, LG>(a) : run_shape<PM, N, W, false, LG>(a);
+  }
 };
-template <bool E>
-struct RunProposers {
-  const Args& a;
-  template <int PM>
-  int proposers() const { return lane_shape(a.cfg, RunShape<PM, E>{a}, -1); }
-};
-int dispatch(const Args& a) {
-  return (a.cfg->flags & PXB_CFG_TRACE_PRODUCTION) ? lane_proposers(a.cfg, RunProposers<true>{a}, -1)
-                                                   : lane_proposers(a.cfg, RunProposers<false>{a}, -1);
-}
+int dispatch(const Args& a) { return host_lane_shape(a.cfg, Run{a}, -1); }
 #endif
 
 }  // namespace

@@ -1,8 +1,9 @@
 """The lane-kernel families accept exactly the same shapes (csrc/lane_shapes.h):
 pxb_trace_instance, pxb_trace_batch_device, pxb_run_scripted_device,
-pxb_trace_scripted_device, pxb_shrink_batch_device and pxb_explore_device are
-called with an otherwise valid, empty job over a sweep of proposer counts,
-acceptor counts, delays and Tick counts.  A shape with a kernel passes
+pxb_trace_scripted_device, pxb_shrink_batch_device, pxb_explore_device,
+pxb_trace_events_device, pxb_cover_device, pxb_explore_cover_device and
+pxb_shrink_cover_batch_device are called with an otherwise valid, empty job
+over a sweep of proposer counts, acceptor counts, delays and Tick counts.  A shape with a kernel passes
 validation (PXB_E_NODEV without a GPU, PXB_OK with one), a shape without one is
 PXB_E_INVAL, and every family agrees with the table written out here."""
 import ctypes as C
@@ -30,7 +31,7 @@ def test_every_family_accepts_the_same_shapes():
     L = pxb.load()
     gpu = torch.cuda.is_available()
     passes = pxb.PXB_OK if gpu else pxb.PXB_E_NODEV
-    if gpu:                                            # (the traces' empty jobs write offsets[0])
+    if gpu:                                            # (the traces' and the events' empty jobs write offsets[0])
         d_off = torch.zeros(1, dtype=torch.int64, device="cuda:0")
         off_p = C.c_void_p(d_off.data_ptr())
     else:
@@ -39,6 +40,8 @@ def test_every_family_accepts_the_same_shapes():
     rec = np.zeros((64, pxb.TRACE_WORDS), np.uint32)
     n_rec = C.c_uint32(0)
     sp = pxb.pxb_explore_space(1, 1, 0xFE, 0)
+    csp = pxb.pxb_explore_cover_space(1, 1, 0xFE, 0, pxb.pxb_cover_query(0, 0, 0, 0))
+    pred = pxb.pxb_shrink_pred(0xFE, 8, (C.c_uint32 * 2)(0, 0), pxb.pxb_cover_query(0, 0, 0, 0))
     families = {
         "pxb_trace_instance": lambda c: L.pxb_trace_instance(c, 0, C.c_void_p(rec.ctypes.data), len(rec),
                                                              C.byref(n_rec), None),
@@ -50,6 +53,15 @@ def test_every_family_accepts_the_same_shapes():
                                                                        None, None, None),
         "pxb_explore_device": lambda c: L.pxb_explore_device(c, None, 0, 1, C.byref(sp), 0, None, 0,
                                                              C.c_void_p(nm.ctypes.data), None, None, None),
+        "pxb_trace_events_device": lambda c: L.pxb_trace_events_device(c, None, 0, 1, None, None, 0, off_p, None, None,
+                                                                       None),
+        "pxb_cover_device": lambda c: L.pxb_cover_device(c, None, 0, 1, None, None, None, None, None),
+        "pxb_explore_cover_device": lambda c: L.pxb_explore_cover_device(c, None, 0, 1, C.byref(csp), 0, None, 0,
+                                                                         C.c_void_p(nm.ctypes.data), None, None, None,
+                                                                         None),
+        "pxb_shrink_cover_batch_device": lambda c: L.pxb_shrink_cover_batch_device(c, None, 0, 1, C.byref(pred), None,
+                                                                                   None, None, None, None, None, None,
+                                                                                   None),
     }
     wrong = []
     for P in PROPOSERS:
