@@ -348,7 +348,6 @@ struct EvLane : Src {
   uint32_t rk[20];                    // Philox round keys (set_keys): uniform, held in VGPRs
   // ---- instance ----
   uint32_t mode;
-  uint32_t gid;                       // instance index within the launch
   uint32_t lo, hi;                    // global instance id (Philox counter words 0, 1)
   uint32_t P, dmax, loss_m1;
   bool lossy;
@@ -448,6 +447,31 @@ struct EvLane : Src {
     __asm__ volatile("");
 #endif
   }
+  // A lane mask that feeds a shift (round 10): the select makes the operand
+  // to shift (0 / 1, 0 / a constant, or 0 / -1 to clear a bit known to be
+  // set: x - (1 << sh) = x + (-1 << sh)) and one instruction shifts and
+  // combines, v_lshl_or_b32 / v_lshl_add_u32, instead of select, shift and a
+  // separate OR / XOR / AND.  (in asm: LLVM moves the shift into the select's
+  // operands, a shift of the constant first, and then has three again;
+  // PXB_EV_C_SHIFTS: the C forms, for an A/B)
+  __host__ __device__ static __forceinline__ uint32_t lshl_or(uint32_t mv, uint32_t sh, uint32_t y) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PXB_EV_C_SHIFTS)
+    uint32_t r;
+    __asm__("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mv), "v"(sh), "v"(y));
+    return r;
+#else
+    return (mv << (sh & 31u)) | y;
+#endif
+  }
+  __host__ __device__ static __forceinline__ uint32_t lshl_add(uint32_t mv, uint32_t sh, uint32_t y) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PXB_EV_C_SHIFTS)
+    uint32_t r;
+    __asm__("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(r) : "v"(mv), "v"(sh), "v"(y));
+    return r;
+#else
+    return (mv << (sh & 31u)) + y;
+#endif
+  }
   // Selects by a per-lane index q over a small register array, as bit
   // operations on the one-hot word 1 << q: element i's lane mask is bit i of
   // it sign-extended (one v_bfe_i32), merged with v_bfi_b32.  A compare per
@@ -507,6 +531,54 @@ struct EvLane : Src {
   template <int K>
   __host__ __device__ static __forceinline__ void put(uint32_t (&v)[K], uint32_t q, uint32_t x) {
     set_from<K>(v, 1u << q, x);
+  }
+
+  // The same selects with the K one-hot lane masks made once and kept (round
+  // 10): the acceptor op reads two arrays at index a and writes one back some
+  // hundred instructions later, past the Execute branch, and LLVM re-made the
+  // masks for the write (K v_bfe_i32) instead of holding them.  hold() pins
+  // them in their registers up to the write.
+  template <int K>
+  struct Masks {
+    uint32_t m[K];
+  };
+  template <int K, int I = 0>
+  __host__ __device__ static __forceinline__ void masks_from(Masks<K>& mk, uint32_t oh) {
+    if constexpr (I < K) {
+      mk.m[I] = lane_mask<I>(oh);
+      masks_from<K, I + 1>(mk, oh);
+    }
+  }
+  template <int K>
+  __host__ __device__ static __forceinline__ Masks<K> masks_of(uint32_t q) {
+    Masks<K> mk;
+    masks_from<K>(mk, 1u << q);
+    return mk;
+  }
+  template <int K>
+  __host__ __device__ static __forceinline__ void hold(Masks<K>& mk) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int i = 0; i < K; ++i) __asm__ volatile("" : "+v"(mk.m[i]));
+#endif
+  }
+  template <int K>
+  __host__ __device__ static __forceinline__ uint32_t get(const uint32_t (&v)[K], const Masks<K>& mk) {
+    uint32_t r = v[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i) r = bfi(mk.m[i], v[i], r);
+    return r;
+  }
+  template <int K>
+  __host__ __device__ static __forceinline__ void put(uint32_t (&v)[K], const Masks<K>& mk, uint32_t x) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      __asm__("v_bfi_b32 %0, %1, %2, %0" : "+v"(v[i]) : "v"(mk.m[i]), "v"(x));
+#else
+      v[i] = bfi(mk.m[i], x, v[i]);
+#endif
+    }
   }
 
   // the reference-count nibble of q's ring slot k, and adding d to it
@@ -648,6 +720,16 @@ struct EvLane : Src {
 #endif
     }
   }
+  // the instance's proposer count and largest delay: drawn per instance in a
+  // fuzzed batch, else the launch's; a simple schedule is never fuzzed
+  // (ev_layouts.h layout_serves), so its lanes read the launch parameters
+  // (scalars) and carry neither
+  __host__ __device__ __forceinline__ uint32_t dmax_of(const EvParams& kp) const { return SP ? kp.delay_max : dmax; }
+  __host__ __device__ __forceinline__ uint32_t nprop_of(const EvParams& kp) const { return SP ? kp.n_prop : P; }
+  // the instance's index within the launch (an id list's entry too): init
+  // makes the counter word from first_instance + index, so the index is not
+  // carried through the iterations (a VGPR the loop never reads)
+  __host__ __device__ __forceinline__ uint32_t gid_of(const EvParams& kp) const { return lo - (uint32_t)kp.first_instance; }
   __host__ __device__ __forceinline__ uint4 draw(uint32_t c2, uint32_t c3) const {
     if constexpr (Src::kPhilox) return philox_rk(lo, hi, c2, c3, rk);
     else return Src::source_draw(lo, hi, c2, c3, rk);
@@ -659,7 +741,6 @@ struct EvLane : Src {
   // so one scalar branch; the loads go first, so that the rest of init hides
   // their latency.
   __host__ __device__ __forceinline__ void init(const EvParams& kp, uint32_t g, const uint32_t* wsrc = nullptr) {
-    gid = g;
     if (wsrc) {
       const uint32_t* const row = wsrc + (uint64_t)g * N;
 #pragma unroll
@@ -863,7 +944,7 @@ struct EvLane : Src {
     const bool snd = isR | csnd;
     PXB_EV_PROBE(EVP_SEND1, snd);
     const bool ok = !(kLossy & lossy & (w.x <= loss_m1));
-    const uint32_t d = 1u + mulhi_n(w.y, dmax);
+    const uint32_t d = 1u + mulhi_n(w.y, dmax_of(kp));
     const bool go = snd & ok;
     const uint32_t base = isR ? (uint32_t)s : sb;   // the send step (a carried copy's is s - 1)
     const uint32_t b4 = base & 15u;
@@ -972,8 +1053,8 @@ struct EvLane : Src {
     const bool now = EARLY & !isR & (base + due_rel == (uint32_t)s);
     const uint32_t slot = (base + due_rel) & WM;
     m.orw(S::WHEEL + slot * S::WW + ((S::WW == 2 && isR) ? 1u : 0u), (go & !now) ? 1u << (isR ? rp.bit : Lq) : 0u);
-    occ |= (go & !now) ? (OCC1 << slot) : 0u;
-    acc_mask |= (go & now) ? (1u << Lq) : 0u;
+    occ = lshl_or((go & !now) ? OCC1 : 0u, slot, occ);
+    acc_mask = lshl_or((go & now) ? 1u : 0u, Lq, acc_mask);
   }
 
   // the Philox counter words of the next copy (seq = the broadcast's index on
@@ -1003,7 +1084,7 @@ struct EvLane : Src {
     }
     // (w: the draw of copy_ctr() taken before this call)
     const bool ok = !(kLossy & lossy & (w.x <= loss_m1));
-    const uint32_t d = 1u + mulhi_n(w.y, dmax);      // (delay_max <= 1: always 1)
+    const uint32_t d = 1u + mulhi_n(w.y, dmax_of(kp));      // (delay_max <= 1: always 1)
     // enqueue (predicated: inactive lanes store to the dummy word)
     const bool go = snd & ok;
     const uint32_t Lq = mulc<PM>(ca) + cp;
@@ -1023,8 +1104,8 @@ struct EvLane : Src {
     const bool now = EARLY & (sb + due_rel == (uint32_t)s);
     const uint32_t slot = (sb + due_rel) & WM;
     m.orw(S::WHEEL + slot * S::WW, (go & !now) ? 1u << Lq : 0u);
-    occ |= (go & !now) ? (OCC1 << slot) : 0u;
-    acc_mask |= (go & now) ? (1u << Lq) : 0u;
+    occ = lshl_or((go & !now) ? OCC1 : 0u, slot, occ);
+    acc_mask = lshl_or((go & now) ? 1u : 0u, Lq, acc_mask);
   }
 
   // One iteration: the proposer part, a copy, the acceptor part, another
@@ -1114,8 +1195,8 @@ struct EvLane : Src {
     // entries, length and reply seq, adjusted in place)
     const uint32_t rq2 = ((wq & ((1u << S::QL) - 1u)) >> S::EB) + ((wq & ~((1u << S::QL) - 1u)) - (1u << S::QL));
     const bool keep = (len > 1u) & (((wq >> (S::EB + S::SB)) & DM) == (s4 & DM));   // the next entry due now too
-    // (bit L, the lowest of ready, is set in acc_mask whenever acc: an XOR clears it)
-    acc_mask ^= ((acc & !keep) ? 1u : 0u) << L;
+    // (bit L, the lowest of ready, is set in acc_mask whenever acc: adding -1 << L clears it)
+    acc_mask = lshl_add((acc & !keep) ? ~0u : 0u, L, acc_mask);
     uint32_t kind, x, z;
     if constexpr (LG) {
       const uint32_t w32 = m.ld(S::BRING + p * S::BR + bslot);
@@ -1125,15 +1206,17 @@ struct EvLane : Src {
       kind = w16 >> 14, x = w16 & 0xFFFu, z = (w16 >> 12) & 3u;
     }
     ref_add(p, bslot, acc ? ~0u : 0u);
-    const uint32_t A = get(accw, a);
+    Masks<N> am = masks_of<N>(a);
+    const uint32_t A = get(accw, am);
     const bool dead = ((A >> A_DEAD) & 1u) != 0u;
-    const uint32_t wa = get(win, a);                 // isolated at s: c0 <= s < c1 (SEMANTICS §4)
+    const uint32_t wa = get(win, am);                // isolated at s: c0 <= s < c1 (SEMANTICS §4)
     const bool isol = ((wa & 0xFFFFu) <= (uint32_t)s) & ((uint32_t)s < (wa >> 16));
     const bool live = acc & !dead & !isol;
     const uint32_t rb = (kind == PROPOSE) ? 12u : 8u;
     canon += acc ? (live ? 2u * rb + 32u : rb) : 0u;
     const uint32_t t_max = A & 0xFFFu;
-    const uint32_t V = LG ? get(accv, a) : A;
+    uint32_t V = A;
+    if constexpr (LG) V = get(accv, am);
     const uint32_t val = LG ? V & 0x3FFFu : (A >> 24) & 3u;
     uint32_t log_len = V >> A_LEN;
     const bool is_ask = live & (kind == ASK), is_prop = live & (kind == PROPOSE), is_exec = live & (kind == EXECUTE);
@@ -1163,7 +1246,7 @@ struct EvLane : Src {
       if (LG || run) {                               // executed <>= [c]: log, digest, divergence
         if (log_len >= A_LEN_MAX) bailed = true;
         PXB_EV_PROBE(EVB_LOG, log_len >= A_LEN_MAX);
-        put(accd, a, fnv_u32(get(accd, a), code_of(val)));
+        put(accd, am, fnv_u32(get(accd, am), code_of(val)));
         if constexpr (LG) {                            // the canonical log's first LOG_TRACK positions (LDS)
           // (straight-line: compare or append at position log_len, the halfword
           // stored back when neither; a position past LOG_TRACK only flags.
@@ -1214,10 +1297,11 @@ struct EvLane : Src {
       const uint32_t c_gr = (A & ~0xFFFu) | x, c_ac = (A & ~0xFFF000u) | (x << 12);
       uint32_t An = accept ? c_ac : Ah;
       An = grant ? c_gr : An;
-      put(accw, a, An);
+      hold(am);
+      put(accw, am, An);
       const uint32_t v_ac = (V & ~0x3FFFu) | z;
       const uint32_t Vn = accept ? v_ac : Vh;
-      put(accv, a, Vn);
+      put(accv, am, Vn);
       const uint32_t p_gr = x | (A & 0xFFF000u) | (R1OK << 30), p_hv = (A & 0xFFFu) | (HAVE << 30);
       constexpr uint32_t p_ac = R2S << 30;
       pw = accept ? p_ac : p_hv;
@@ -1232,7 +1316,8 @@ struct EvLane : Src {
       const uint32_t c_gr = (A & ~0xFFFu) | x, c_ac = (A & 0xFC000FFFu) | (x << 12) | (z << 24);
       uint32_t An = accept ? c_ac : Ah;
       An = grant ? c_gr : An;
-      put(accw, a, An);
+      hold(am);
+      put(accw, am, An);
       const uint32_t p_gr = x | (A & 0x03FFF000u) | (R1OK << 30), p_hv = (A & 0xFFFu) | (HAVE << 30);
       constexpr uint32_t p_ac = R2S << 30;
       pw = accept ? p_ac : p_hv;
@@ -1288,14 +1373,15 @@ struct EvLane : Src {
       const uint32_t pe0 = m.ld(S::POOLB + ((S::TE_SAFE || !kc) ? k : 0u));
       const uint32_t pn = m.ld(S::POOLB + ((S::TE_SAFE || !nkc) ? nk : 0u));
       const uint32_t pe = kc ? (R2S << 30) : pe0;
-      pfree |= (resp & !kc) ? ((pool_mask_t)1 << k) : (pool_mask_t)0;
+      if constexpr (sizeof(pool_mask_t) == 4) pfree = lshl_or((resp & !kc) ? 1u : 0u, k, (uint32_t)pfree);
+      else pfree |= (resp & !kc) ? ((pool_mask_t)1 << k) : (pool_mask_t)0;
       const uint32_t popped = S::RZ ? rr >> S::IB
                                     : ((rr & ((1u << S::RL) - 1u)) >> S::IB) + ((rr & ~((1u << S::RL) - 1u)) - (1u << S::RL));
       rsp_st(Lr, resp ? popped : rr);                // (popped: entries down one, length - 1)
       const bool nnow = nkc ? ((nk & 7u) == (s4 & 7u)) : (((pn >> 26) & 15u) == s4);
       const bool rkeep = resp & (S::RH ? rr >= (1u << (2 * S::IB)) : S::RZ ? nk != 0u : rlen > 1u) & nnow;
-      // (bit j is set whenever pin: clearing it is an XOR of the shifted predicate)
-      in_mask ^= ((pin & !rkeep) ? 1u : 0u) << j;
+      // (bit j is set whenever pin: clearing it is adding -1 << j)
+      in_mask = lshl_add((pin & !rkeep) ? ~0u : 0u, j, in_mask);
       const uint32_t rkind = pe >> 30, px = pe & 0xFFFu, py = (pe >> 12) & 0xFFFu;
       const uint32_t kz = k - (uint32_t)S::POOLB_SHIFT;   // (the pool index of entry k)
       const uint32_t pz = LG ? m.ld16h(S::POOLZ + ((kz >> 1) & 31u), kz & 1u) : (pe >> 24) & 3u;
@@ -1413,7 +1499,7 @@ struct EvLane : Src {
       PXB_EV_PROBE(EVP_FIN, quiet | capped);
       if (__builtin_expect(quiet | capped, 0)) {
         s = capped ? (int32_t)kp.step_cap - 1 : (back ? s - 1 : s);
-        finish(capped, o);
+        finish(kp, capped, o);
         fin(o);
         return true;
       }
@@ -1434,12 +1520,12 @@ struct EvLane : Src {
   }
 
   // ---- outputs of an ended instance (SEMANTICS §7) ----
-  __host__ __device__ __forceinline__ void finish(bool capped, EvOut& o) {
+  __host__ __device__ __forceinline__ void finish(const EvParams& kp, bool capped, EvOut& o) {
     const uint32_t steps = (uint32_t)s + 1u;
     uint32_t f = lflags | (capped ? (uint32_t)PXB_F_STEP_CAP : 0u) | (dval ? 0u : (uint32_t)PXB_F_UNDECIDED);
 #pragma unroll
     for (int p = 0; p < PM; ++p)
-      f |= (!capped && (uint32_t)p < P && p_state(p) != IDLE) ? (uint32_t)PXB_F_STUCK : 0u;
+      f |= (!capped && (uint32_t)p < nprop_of(kp) && p_state(p) != IDLE) ? (uint32_t)PXB_F_STUCK : 0u;
     // (a panic is what sets an acceptor's dead bit, and nothing clears it)
     uint32_t dead = 0u;
 #pragma unroll

@@ -183,6 +183,73 @@ struct EvTotals {
   }
 };
 
+// The 0 / 1-per-instance sums of the per-lane kernel (instances, undecided,
+// stuck, panic, divergence, step cap; log mode: log-trunc too) as 10-bit
+// fields, three to a word, in tot_slot order: field k at bit 10 (k % 3) of
+// word k / 3.  A lane takes at most EV_FLUSH instances between flushes, so a
+// field never carries into its neighbour.  The sums live in VGPRs through the
+// whole iteration loop and are touched only in its finishing branch: packed
+// they hold 2 registers instead of 6 (round 10).  Plain C++: the host test
+// (tests/test_ev_valu_forms.py) runs it against plain sums.
+constexpr uint32_t EV_PKB = 10, EV_PKM = (1u << EV_PKB) - 1u;
+constexpr int EV_NFLAG = 6;                   // the 0 / 1 sums every mode has (log mode: + log-trunc)
+static_assert(EV_FLUSH <= EV_PKM, "a packed 0 / 1 sum holds a lane's instances between two flushes");
+template <bool LG>
+struct EvFlagSums {
+  static constexpr int NF = EV_NFLAG + (LG ? 1 : 0), NW = (NF + 2) / 3;
+  uint32_t w[NW];
+  __host__ __device__ void clear() {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = 0u;
+  }
+  // one finished instance with the PXB_F_* flags f: one packed addend per word
+  __host__ __device__ void add(uint32_t f) {
+    constexpr uint32_t F[7] = {0u, PXB_F_UNDECIDED, PXB_F_STUCK, PXB_F_PANIC, PXB_F_LOG_DIVERGENCE, PXB_F_STEP_CAP,
+                               PXB_F_LOG_TRUNC};
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      uint32_t a = 0u;
+#pragma unroll
+      for (int k = 3 * i; k < 3 * i + 3 && k < NF; ++k) a |= ((k == 0 || (f & F[k])) ? 1u : 0u) << (EV_PKB * (k % 3));
+      w[i] += a;
+    }
+  }
+  // sum k in tot_slot order (0: instances ... 5: step cap, 6: log-trunc)
+  __host__ __device__ uint32_t get(int k) const { return k < NF ? (w[k / 3] >> (EV_PKB * (k % 3))) & EV_PKM : 0u; }
+  __host__ __device__ uint32_t instances() const { return w[0] & EV_PKM; }
+};
+
+// The per-lane kernel's run totals: the packed 0 / 1 sums, the four 32-bit
+// sums (rounds, steps, messages, executes) and the canonical bytes
+template <bool LG>
+struct EvPackedTotals {
+  EvFlagSums<LG> fl;
+  uint32_t c[4];                      // tot_slot[6 .. 9]
+  uint64_t canon;
+  __device__ void clear() {
+    fl.clear();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) c[q] = 0u;
+    canon = 0ull;
+  }
+  // the wave's sums into its partial row (all 64 lanes of the wave call this);
+  // the fields are unpacked before the wave sums
+  __device__ void flush(unsigned long long* trow, uint32_t lane) {
+#pragma unroll
+    for (int q = 0; q < EV_NTOT - 1; ++q) {
+      if (q == 10 && !LG) continue;
+      const uint32_t v = q < EV_NFLAG ? fl.get(q) : q < 10 ? c[q - EV_NFLAG] : fl.get(EV_NFLAG);
+      const uint64_t t = EvTotals::wave_sum((uint64_t)v);
+      if (lane == 0 && t) atomicAdd(&trow[tot_slot[q]], (unsigned long long)t);
+    }
+    const uint64_t t = EvTotals::wave_sum(canon);
+    if (lane == 0 && t) atomicAdd(&trow[PXB_C_CANON_BYTES], (unsigned long long)t);
+    const uint64_t d = EvTotals::wave_sum((uint64_t)(fl.get(0) - fl.get(1)));   // decided = instances - undecided
+    if (lane == 0 && d) atomicAdd(&trow[PXB_C_DECIDED], (unsigned long long)d);
+    clear();
+  }
+};
+
 // The compact layout leaves room for 10 resident waves per CU (LDS), i.e. 3
 // on some SIMDs: its register budget is then 168 VGPRs, which the second
 // bound (minimum waves per SIMD) makes the compiler keep to.
@@ -194,7 +261,7 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
   __shared__ uint32_t lds[S::WORDS * 64];
   const uint32_t lane = threadIdx.x;
   unsigned long long* const trow = kp.part + (size_t)(blockIdx.x % EV_TCOPIES) * 16u;
-  EvTotals tot;
+  EvPackedTotals<LG> tot;
   tot.clear();
   EvLane<PM, N, POOL, W, CMP, LdsMem, true, LG, SL, SP> L;
   L.m = LdsMem{lds, lane};
@@ -247,7 +314,7 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
       uint64_t freeb = __builtin_amdgcn_ballot_w64(L.mode == M_IDLE);
       while (freeb != 0ull && !drained) {
         // (wave-uniform; a lane's sums only grow by instances it takes here)
-        if (__builtin_amdgcn_ballot_w64(tot.c[0] >= EV_FLUSH) != 0ull) tot.flush(trow, lane);
+        if (__builtin_amdgcn_ballot_w64(tot.fl.instances() >= EV_FLUSH) != 0ull) tot.flush(trow, lane);
         if (next >= end) {
           uint32_t c = 0;
           if (lane == 0) c = atomicAdd(kp.queue, EV_QCHUNK);
@@ -269,7 +336,7 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
         if (((freeb >> lane) & 1ull) && rank < take) {
           if (__builtin_expect(L.bailed, 0)) {   // (a fuzzed P above this shape's: the general kernel's)
             const uint32_t pos = atomicAdd(kp.bail_n, 1u);
-            if (pos < kp.bail_cap) kp.bail_ids[pos] = L.gid;
+            if (pos < kp.bail_cap) kp.bail_ids[pos] = L.gid_of(kp.p);
             L.mode = M_IDLE;
             L.bailed = false;
           }
@@ -292,30 +359,24 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
     // (an instance that bailed in its last iteration is re-run: no outputs here)
     auto fin = [&](const EvOut& o) {
         if (L.bailed) return;
-        const uint32_t f = o.flags;
-        tot.c[0] += 1u;
-        tot.c[1] += (f & PXB_F_UNDECIDED) ? 1u : 0u;
-        tot.c[2] += (f & PXB_F_STUCK) ? 1u : 0u;
-        tot.c[3] += (f & PXB_F_PANIC) ? 1u : 0u;
-        tot.c[4] += (f & PXB_F_LOG_DIVERGENCE) ? 1u : 0u;
-        tot.c[5] += (f & PXB_F_STEP_CAP) ? 1u : 0u;
-        tot.c[6] += L.rounds;
-        tot.c[7] += o.steps;
-        tot.c[8] += L.msgs_sent();
-        tot.c[9] += L.execs;
-        if (LG) tot.c[10] += (f & PXB_F_LOG_TRUNC) ? 1u : 0u;
+        tot.fl.add(o.flags);
+        tot.c[0] += L.rounds;
+        tot.c[1] += o.steps;
+        tot.c[2] += L.msgs_sent();
+        tot.c[3] += L.execs;
         tot.canon += L.canon;
-        if (kp.out) kp.out[L.gid] = make_uint4(o.res[0], o.res[1], o.res[2], o.res[3]);
+        const uint32_t gid = L.gid_of(kp.p);
+        if (kp.out) kp.out[gid] = make_uint4(o.res[0], o.res[1], o.res[2], o.res[3]);
         if (kp.dig) {
 #pragma unroll
-          for (int a = 0; a < N; ++a) kp.dig[(uint64_t)L.gid * N + a] = L.digest_of(a);
+          for (int a = 0; a < N; ++a) kp.dig[(uint64_t)gid * N + a] = L.digest_of(a);
         }
         if (kp.acc) {
 #pragma unroll
           for (int a = 0; a < N; ++a) {
             uint32_t r[4];
             L.record_of(a, r);
-            kp.acc[(uint64_t)L.gid * N + a] = make_uint4(r[0], r[1], r[2], r[3]);
+            kp.acc[(uint64_t)gid * N + a] = make_uint4(r[0], r[1], r[2], r[3]);
           }
         }
     };
@@ -331,7 +392,7 @@ __global__ __launch_bounds__(64, CMP ? 3 : SL ? 2 : 1) void paxos_ev_kernel(EvKP
     } while (__builtin_amdgcn_ballot_w64(done | L.bailed) == 0ull);
     if (__builtin_expect(L.bailed, 0)) {      // beyond this kernel's capacities: re-run by the general kernel
       const uint32_t pos = atomicAdd(kp.bail_n, 1u);
-      if (pos < kp.bail_cap) kp.bail_ids[pos] = L.gid;
+      if (pos < kp.bail_cap) kp.bail_ids[pos] = L.gid_of(kp.p);
       L.mode = M_IDLE;
       L.bailed = false;
     }

@@ -77,7 +77,7 @@ void model(const pxb_config* cfg, uint32_t n, uint32_t refill_min, const std::ve
           ++next;
           ++inits;
           if (L[l].bailed) {
-            if (bailed_out) bailed_out->push_back(L[l].gid);
+            if (bailed_out) bailed_out->push_back(L[l].gid_of(p));
             L[l].mode = M_IDLE;
             L[l].bailed = false;
             ++bails;
@@ -102,7 +102,7 @@ void model(const pxb_config* cfg, uint32_t n, uint32_t refill_min, const std::ve
       orb |= ev_probe_bits;
       for (int b = 0; b < NB; ++b) sum[b] += (ev_probe_bits >> b) & 1u;
       if (L[l].bailed) {
-        if (bailed_out) bailed_out->push_back(L[l].gid);
+        if (bailed_out) bailed_out->push_back(L[l].gid_of(p));
         for (int b = 0; b < 6; ++b) bcause[b] += (ev_probe_bits >> (16 + b)) & 1u;
         L[l].mode = M_IDLE;
         L[l].bailed = false;
