@@ -8,8 +8,10 @@ import dataclasses
 import numpy as np
 import pytest
 
+import ev_matrix as M
 import pxb
 import script_oracle as SO
+from test_ev_matrix import lane_host
 from test_trace_batch_host import SELECTIONS
 
 pytestmark = pytest.mark.gpu
@@ -261,3 +263,19 @@ def test_g8_every_kernel_unit_launches(gpu_lib, P, N, delay_max):
         nk = int(h["n_kept"][i])
         assert len(g) == min(nk, 2) and np.array_equal(g, h["rec"][i][nk - len(g):nk]), i
     assert (status == pxb.TRACE_OK).sum() >= 32
+
+
+@pytest.mark.parametrize("P,N,mode", M.LANE_SHAPES, ids=M.LANE_SHAPE_IDS)
+def test_g9_every_shape_equals_the_oracle(gpu_lib, P, N, mode):
+    """Every shape of the family (csrc/lane_shapes.h: P in 1..3, N in 2..9, both
+    wheels and log mode) on g8's lossy schedule: 128 all-keep rows give the
+    oracle's results, digests and acceptor records on every row that ends OK,
+    at least 7/8 of the rows do, and the statuses are the host build's."""
+    cfg = M.lane_cfg(P, N, mode)
+    rows, h = lane_host(P, N, mode)
+    eres, edig, eacc = M.lane_oracle(P, N, mode)
+    res, dig, acc, status, sent = pxb.run_scripted(cfg, rows, M.LANE_DEPTH, want_acceptors=True)
+    ok = status == pxb.TRACE_OK
+    assert int((~ok).sum()) <= M.LANE_CAP
+    assert np.array_equal(res[ok], eres[ok]) and np.array_equal(dig[ok], edig[ok]) and np.array_equal(acc[ok], eacc[ok])
+    assert np.array_equal(status, h["status"]) and np.array_equal(sent, h["sent"])

@@ -7,6 +7,7 @@ import dataclasses
 import numpy as np
 import pytest
 
+import ev_matrix as M
 import pxb
 from test_trace_batch_host import SELECTIONS, U32, check_against_oracle, select
 
@@ -250,3 +251,20 @@ def test_capped_instance_records_its_last_visited_step(gpu_lib, production):
         check_against_oracle(pxb.trace_records(rec), r, cfg, 33)
     tail = pxb.trace_batch(cfg, [33], tail=1, production=production)[0]
     assert len(tail) == 1 and np.array_equal(tail[0], rec[-1])
+
+
+@pytest.mark.parametrize("P,N,mode", M.LANE_SHAPES, ids=M.LANE_SHAPE_IDS)
+def test_every_shape_equals_the_oracle(gpu_lib, P, N, mode):
+    """Every shape of the family (csrc/lane_shapes.h: P in 1..3, N in 2..9, both
+    wheels and log mode) on the lossy schedule of tests/ev_matrix.py: 128
+    consecutive ids, their last record each.  The result of every id that ends
+    OK is the oracle's, at least 7/8 of the ids do, and an OK id's one record is
+    its last step's."""
+    cfg = M.lane_cfg(P, N, mode)
+    eres = M.lane_oracle(P, N, mode)[0]
+    rec, offs, status, res = pxb.trace_batch(cfg, M.LANE_IDS, tail=1)
+    ok = status == pxb.TRACE_OK
+    assert int((~ok).sum()) <= M.LANE_CAP
+    assert np.array_equal(res[ok], eres[ok])
+    assert offs[-1] == len(rec) and (np.diff(offs.astype(np.int64))[ok] == 1).all()
+    assert np.array_equal(rec[offs[:-1][ok].astype(np.int64), 0], (eres[ok][:, 3] >> 16) - 1)
