@@ -52,6 +52,7 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "../../include/paxos_batch.h"
 #include "ev_layouts.h"
@@ -66,8 +67,39 @@ namespace ev {
 #ifndef PXB_EV_LG_RH
 #define PXB_EV_LG_RH 0
 #endif
+// How a lane that does not write a link or payload word leaves it alone:
+//   0  a branch around the store (an exec-mask branch per site: measured a loss)
+//   1  every lane stores; a lane that does not write stores the old value back
+//      (a select per site, and for the broadcast's payloads a load each)
+//   2  lane-masked stores (round 11): the accessor's st_if / st16h_if / sth_if
+//      store under the predicate, so the select and every load that only fed
+//      it go; PXB_EV_ST_IF_SITES picks the sites (the others stay form 1)
 #ifndef PXB_EV_STORE_BACK
-#define PXB_EV_STORE_BACK 1
+#define PXB_EV_STORE_BACK 2
+#endif
+// the sites of form 2, one bit each: copy_send's request word, send_first's
+// link words, send_first's pool word, broadcast's payloads, the proposer op's
+// response link, the acceptor op's request link
+#define PXB_EV_SI_COPY 1
+#define PXB_EV_SI_SEND 2
+#define PXB_EV_SI_POOL 4
+#define PXB_EV_SI_BCAST 8
+#define PXB_EV_SI_PROP 16
+#define PXB_EV_SI_ACC 32
+// Default: the two that measured as gains on MI355X, the acceptor op's request
+// link and the broadcast's payloads (tight layout, config 4 at 2^26: -0.6 %
+// kernel time each, -1.5 % together).  Each of the others prices at 0 or -1
+// VALU and measured slower on top of these two: copy +0.2 %, pool +0.5 %, the
+// proposer op's +0.8 %, send_first's links +1.3 % -- a masked store is two
+// SALU writes of exec around the store, and pays only where it takes more off
+// the path than a select.
+#ifndef PXB_EV_ST_IF_SITES
+#define PXB_EV_ST_IF_SITES (PXB_EV_SI_BCAST | PXB_EV_SI_ACC)
+#endif
+// (form 1's pool store goes to the link word when no pool entry is free and
+// relies on the link's store-back to rewrite it)
+#if (PXB_EV_ST_IF_SITES & PXB_EV_SI_SEND) && !(PXB_EV_ST_IF_SITES & PXB_EV_SI_POOL)
+#error "PXB_EV_SI_SEND needs PXB_EV_SI_POOL"
 #endif
 #ifndef PXB_EV_PQ_CAP
 #define PXB_EV_PQ_CAP 4
@@ -326,6 +358,38 @@ template <class T, class = void>
 struct draws_tap : std::false_type {};
 template <class T>
 struct draws_tap<T, std::void_t<decltype(T::kTap)>> : std::integral_constant<bool, T::kTap> {};
+
+// Whether a memory accessor has the lane-masked stores st_if / st16h_if /
+// sth_if (LdsMem; the host accessors that check them).  One without them gets
+// a guarded plain store, which is what they mean.
+template <class M, class = void>
+struct mem_has_st_if : std::false_type {};
+template <class M>
+struct mem_has_st_if<M, std::void_t<decltype(std::declval<const M&>().st_if(0u, 0u, true))>> : std::true_type {};
+// The predicate of a lane-masked store.  On the device it is the wave's
+// 64-bit lane mask, made one compare at a time and combined with & and |:
+// the ballot of a single compare is that v_cmp's own SGPR result, and the
+// combining is SALU, while the ballot of an already combined predicate costs
+// a v_cndmask 0, 1 and a v_cmp to get the mask back.
+// On the host it is the lane's own bool.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned long long lanes_t;
+__device__ __forceinline__ lanes_t lanes(bool c) { return __builtin_amdgcn_ballot_w64(c); }
+// (the lane's own bit: for an accessor without the masked stores)
+__device__ __forceinline__ bool lanes_mine(lanes_t m) {
+  return ((m >> __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))) & 1ull) != 0ull;
+}
+#else
+typedef bool lanes_t;
+inline lanes_t lanes(bool c) { return c; }
+inline bool lanes_mine(lanes_t m) { return m; }
+#endif
+// ... and whether it has them as templates over a compile-time word base
+template <class M, class = void>
+struct mem_has_st_if_at : std::false_type {};
+template <class M>
+struct mem_has_st_if_at<M, std::void_t<decltype(std::declval<const M&>().template st_if<1u>(0u, 0u, lanes_t()))>>
+    : std::true_type {};
 
 // EARLY: a step may end with the copies of its last broadcast still to send
 // (see end_op); the trace kernel turns it off so that its per-step records
@@ -653,6 +717,37 @@ struct EvLane : Src {
     if constexpr (S::RH) m.sth(S::RSP, Lr, v);
     else m.st(S::RSP + Lr, v);
   }
+  // ---- lane-masked stores (PXB_EV_STORE_BACK 2): only the lanes with c store ----
+  __host__ __device__ static constexpr bool st_if_site(int bit) {
+    return PXB_EV_STORE_BACK == 2 && (PXB_EV_ST_IF_SITES & bit) != 0;
+  }
+  // (word BASE + i.  An accessor with the stores as templates over BASE --
+  // LdsMem -- takes the lane mask and puts BASE into the store's offset field;
+  // one with plain st_if / st16h_if / sth_if, or with none, takes the lane's
+  // own predicate: the host accessors)
+  template <uint32_t BASE>
+  __host__ __device__ __forceinline__ void st_if(uint32_t i, uint32_t v, lanes_t c) const {
+    if constexpr (mem_has_st_if_at<Mem>::value) m.template st_if<BASE>(i, v, c);
+    else if constexpr (mem_has_st_if<Mem>::value) m.st_if(BASE + i, v, lanes_mine(c));
+    else if (lanes_mine(c)) m.st(BASE + i, v);
+  }
+  template <uint32_t BASE>
+  __host__ __device__ __forceinline__ void st16h_if(uint32_t i, uint32_t half, uint32_t v, lanes_t c) const {
+    if constexpr (mem_has_st_if_at<Mem>::value) m.template st16h_if<BASE>(i, half, v, c);
+    else if constexpr (mem_has_st_if<Mem>::value) m.st16h_if(BASE + i, half, v, lanes_mine(c));
+    else if (lanes_mine(c)) m.st16h(BASE + i, half, v);
+  }
+  __host__ __device__ __forceinline__ void rsp_st_if(uint32_t Lr, uint32_t v, lanes_t c) const {
+    if constexpr (mem_has_st_if_at<Mem>::value) {
+      if constexpr (S::RH) m.template sth_if<S::RSP>(0u, Lr, v, c);
+      else m.template st_if<S::RSP>(Lr, v, c);
+    } else if constexpr (mem_has_st_if<Mem>::value) {
+      if constexpr (S::RH) m.sth_if(S::RSP, Lr, v, lanes_mine(c));
+      else m.st_if(S::RSP + Lr, v, lanes_mine(c));
+    } else if (lanes_mine(c)) {
+      rsp_st(Lr, v);
+    }
+  }
 
   // the Tick bits of step t
   __host__ __device__ __forceinline__ uint32_t ticks_at(int32_t t) const {
@@ -731,6 +826,9 @@ struct EvLane : Src {
   // carried through the iterations (a VGPR the loop never reads)
   __host__ __device__ __forceinline__ uint32_t gid_of(const EvParams& kp) const { return lo - (uint32_t)kp.first_instance; }
   __host__ __device__ __forceinline__ uint4 draw(uint32_t c2, uint32_t c3) const {
+    // (c0 = lo in every draw of an instance: LLVM hoists round 0's product of
+    // it out of the iteration loop itself; passed in from init, round 11, the
+    // listing was the same)
     if constexpr (Src::kPhilox) return philox_rk(lo, hi, c2, c3, rk);
     else return Src::source_draw(lo, hi, c2, c3, rk);
   }
@@ -841,7 +939,7 @@ struct EvLane : Src {
           canon += 48u;                              // (the Tick: a proposer input of step 0)
           pw0[p] = 1u | (ROUND1 << 28);
           pw1[p] = ((uint32_t)p + 1u) << 4;
-          broadcast((uint32_t)p, ASK, 1u, 0u, true, 1u, false, 0u);
+          broadcast((uint32_t)p, ASK, 1u, 0u, true, 1u, false, 0u, lanes(true), lanes(false));
         }
       }
       in_mask = 0u;
@@ -852,8 +950,9 @@ struct EvLane : Src {
   // x1, Client.hs:185, only after an Execute] by proposer q: bookkeeping of
   // bcast() (oracle) and pending entries whose N copies go out over the next
   // iterations.  Payloads go to the next ring slots of q.
+  // (p0m, p1m: p0 and p1 as the payload stores' lane masks, lanes())
   __host__ __device__ __forceinline__ void broadcast(uint32_t q, uint32_t kind0, uint32_t x0, uint32_t z0, bool p0,
-                                                     uint32_t x1, bool p1, uint32_t val) {
+                                                     uint32_t x1, bool p1, uint32_t val, lanes_t p0m, lanes_t p1m) {
     rounds += ((p0 & (kind0 == ASK)) ? 1u : 0u) + (p1 ? 1u : 0u);
     const bool ex = p0 & (kind0 == EXECUTE);
     PXB_EV_PROBE(EVP_EXEC, ex);
@@ -884,13 +983,22 @@ struct EvLane : Src {
         if (p1) m.st16h(S::BRING + bring_word(q, slot1), bring_half(q, slot1), x1 | (ASK << 14));
       }
     }
-    if constexpr (LG && PXB_EV_STORE_BACK) {       // (the same with the log mode's payload words)
+    if constexpr (st_if_site(PXB_EV_SI_BCAST)) {
+      // (lane-masked: a lane that makes no broadcast stores nothing, so the
+      // slots' old payloads are not loaded)
+      if constexpr (LG) {
+        st_if<S::BRING>(q * S::BR + slot0, x0 | (z0 << 12) | (kind0 << 30), p0m);
+        st_if<S::BRING>(q * S::BR + slot1, x1 | (ASK << 30), p1m);
+      } else {
+        st16h_if<S::BRING>(bring_word(q, slot0), bring_half(q, slot0), x0 | (z0 << 12) | (kind0 << 14), p0m);
+        st16h_if<S::BRING>(bring_word(q, slot1), bring_half(q, slot1), x1 | (ASK << 14), p1m);
+      }
+    } else if constexpr (LG && PXB_EV_STORE_BACK) {       // (the same with the log mode's payload words)
       const uint32_t w0a = S::BRING + q * S::BR + slot0, w1a = S::BRING + q * S::BR + slot1;
       const uint32_t o0 = m.ld(w0a), o1 = m.ld(w1a);
       m.st(w0a, p0 ? x0 | (z0 << 12) | (kind0 << 30) : o0);
       m.st(w1a, p1 ? x1 | (ASK << 30) : o1);
-    }
-    if constexpr (!LG && PXB_EV_STORE_BACK) {
+    } else if constexpr (!LG && PXB_EV_STORE_BACK) {
       // (without a branch: a lane that makes no broadcast stores the slots'
       // halfwords back; slot1 = slot0 + 1 mod BR, so the two never alias)
       const uint32_t w0a = S::BRING + bring_word(q, slot0), h0a = bring_half(q, slot0);
@@ -990,7 +1098,9 @@ struct EvLane : Src {
       PXB_EV_PROBE(EVB_QFIFO, go & !isR & (qlen >= (uint32_t)S::QC));
       // the pool word: to a free entry (harmless unless a reply goes), or, with
       // none free, to the request word, which the next store rewrites
-      m.st(pfree ? S::POOLB + k2 : S::REQ + Lq, rp.pw | (due4 << 26));
+      // (lane-masked: only with a free entry -- nothing rewrites the request word then)
+      if constexpr (st_if_site(PXB_EV_SI_POOL)) st_if<S::POOLB>(k2, rp.pw | (due4 << 26), lanes(pfree != 0));
+      else m.st(pfree ? S::POOLB + k2 : S::REQ + Lq, rp.pw | (due4 << 26));
       if constexpr (LG) {                            // (entry k2 = pool index + 1; no free entry: the dummy halfword)
         const uint32_t zi = pfree ? k2 - 1u : (uint32_t)POOL;
         m.st16h(S::POOLZ + (zi >> 1), zi & 1u, rp.z);
@@ -999,8 +1109,13 @@ struct EvLane : Src {
       // (the entry replaces the sentinel, the sentinel moves up one entry)
       const uint32_t nR = h + ((ent + (1u << S::IB) - 1u) << msb);
       const uint32_t nQ = wq + (1u << S::QL) + ((cslot | ((due4 & DM) << S::SB)) << ((uint32_t)S::EB * qlen));
-      m.st(S::REQ + Lq, (go & !isR) ? nQ : wq);
-      rsp_st(rp.Lr, (go & isR) ? nR : h);
+      if constexpr (st_if_site(PXB_EV_SI_SEND)) {
+        st_if<S::REQ>(Lq, nQ, lanes(go & !isR));
+        rsp_st_if(rp.Lr, nR, lanes(go & isR));
+      } else {
+        m.st(S::REQ + Lq, (go & !isR) ? nQ : wq);
+        rsp_st(rp.Lr, (go & isR) ? nR : h);
+      }
     } else {
       const uint32_t lw = isR ? S::RSP + rp.Lr : S::REQ + Lq;   // the link word
       const uint32_t wv = m.ld(lw);
@@ -1034,7 +1149,8 @@ struct EvLane : Src {
       PXB_EV_PROBE(EVB_QFIFO, go & !isR & (len >= (uint32_t)S::QC));
       // the pool word: to a free entry (harmless unless a reply goes), or, with
       // none free, to the link word, which the next store rewrites
-      m.st(pfree ? S::POOLB + k2 : lw, rp.pw | (due4 << 26));
+      if constexpr (st_if_site(PXB_EV_SI_POOL)) st_if<S::POOLB>(k2, rp.pw | (due4 << 26), lanes(pfree != 0));
+      else m.st(pfree ? S::POOLB + k2 : lw, rp.pw | (due4 << 26));
       if constexpr (LG) {                            // (no free entry: the dummy halfword)
         const uint32_t zi = pfree ? k2 : (uint32_t)POOL;
         m.st16h(S::POOLZ + (zi >> 1), zi & 1u, rp.z);
@@ -1045,7 +1161,8 @@ struct EvLane : Src {
       const uint32_t nR = S::RZ ? wv | (ent << ((S::IB * len) & 31u))
                                 : ((wv + (1u << S::RL) + (ent << (S::IB * len))) & ~(15u << RD)) | (due4 << RD);
       const uint32_t nQ = wv + (1u << S::QL) + ((cslot | ((due4 & DM) << S::SB)) << ((uint32_t)S::EB * len));
-      m.st(lw, go ? (isR ? nR : nQ) : wv);
+      if constexpr (st_if_site(PXB_EV_SI_SEND)) st_if<0>(lw, isR ? nR : nQ, lanes(go));
+      else m.st(lw, go ? (isR ? nR : nQ) : wv);
     }
     pfree &= (go & isR & !r2c) ? ~((pool_mask_t)1 << k2) : ~(pool_mask_t)0;
     ref_add(cp, cslot, (go & !isR) ? 1u : 0u);
@@ -1068,6 +1185,7 @@ struct EvLane : Src {
     const uint32_t sb = (uint32_t)s - (CARRY2 ? (pqo ? 1u : 0u) : pqo);
     const uint32_t s4 = sb & 15u;
     const bool snd = act & (pq_len != 0u);
+    const lanes_t sndm = lanes(act) & lanes(pq_len != 0u);
     PXB_EV_PROBE(EVP_COPY, snd);
     const uint32_t ce = pq & 31u;
     const uint32_t cp = ce >> 3, cslot = ce & 7u, ca = acur;
@@ -1087,6 +1205,7 @@ struct EvLane : Src {
     const uint32_t d = 1u + mulhi_n(w.y, dmax_of(kp));      // (delay_max <= 1: always 1)
     // enqueue (predicated: inactive lanes store to the dummy word)
     const bool go = snd & ok;
+    const lanes_t gom = sndm & (kLossy ? lanes(!lossy) | lanes(w.x > loss_m1) : lanes(true));
     const uint32_t Lq = mulc<PM>(ca) + cp;
     const uint32_t wq = m.ld(S::REQ + Lq);
     const uint32_t qlen = (wq >> S::QL) & QLM;
@@ -1097,7 +1216,8 @@ struct EvLane : Src {
     const uint32_t ent = cslot | (((s4 + due_rel) & DM) << S::SB);
     // (inactive lanes store their word back unchanged)
     // (entries above the length are 0: a pop shifts zeros in; a full FIFO bails)
-    m.st(S::REQ + Lq, go ? wq + (1u << S::QL) + (ent << ((uint32_t)S::EB * qlen)) : wq);
+    if constexpr (st_if_site(PXB_EV_SI_COPY)) st_if<S::REQ>(Lq, wq + (1u << S::QL) + (ent << ((uint32_t)S::EB * qlen)), gom);
+    else m.st(S::REQ + Lq, go ? wq + (1u << S::QL) + (ent << ((uint32_t)S::EB * qlen)) : wq);
     ref_add(cp, cslot, go ? 1u : 0u);
     // due at s (a carried-over copy with the shortest delay): straight into
     // this step's due links, else into the wheel
@@ -1181,6 +1301,7 @@ struct EvLane : Src {
                                                    uint32_t ready) {
     const uint32_t s4 = (uint32_t)s & 15u;
     const bool acc = act & (ready != 0u);
+    const lanes_t accm = lanes(act) & lanes(ready != 0u);
     PXB_EV_PROBE(EVP_ACC, acc);
     const uint32_t L = acc ? ctz32(ready) : 0u;
     const uint32_t a = L / (uint32_t)PM, p = L - a * (uint32_t)PM;
@@ -1325,7 +1446,8 @@ struct EvLane : Src {
     }
     const bool snd1 = live & !is_exec;              // the reply, on link a -> p
     if constexpr (draws_tap<Src>::value) Src::tap_acc(acc, a, p, kind, x, z, dead ? 1u : isol ? 2u : 0u, snd1, pw, rz);
-    m.st(S::REQ + L, acc ? rq2 + ((S::CMP && snd1) ? 1u << S::KSH : 0u) : wq);
+    if constexpr (st_if_site(PXB_EV_SI_ACC)) st_if<S::REQ>(L, rq2 + ((S::CMP && snd1) ? 1u << S::KSH : 0u), accm);
+    else m.st(S::REQ + L, acc ? rq2 + ((S::CMP && snd1) ? 1u << S::KSH : 0u) : wq);
 
     // ================= the reply, on a -> p (SEMANTICS §5) =================
     // Philox seq = the link's reply count.  Sent before the proposer part so its
@@ -1351,6 +1473,7 @@ struct EvLane : Src {
   __host__ __device__ __forceinline__ void prop_op(const EvParams& kp, bool act) {
     const uint32_t s4 = (uint32_t)s & 15u;
     const bool pin = act & (in_mask != 0u) & (pq_len <= PQ_CAP - 2u);
+    const uint32_t in_mask0 = in_mask;
     PXB_EV_PROBE(EVP_PROP, pin);
     {
       // (pin: in_mask != 0, so the bare count, without ctz32's test for 0)
@@ -1377,7 +1500,10 @@ struct EvLane : Src {
       else pfree |= (resp & !kc) ? ((pool_mask_t)1 << k) : (pool_mask_t)0;
       const uint32_t popped = S::RZ ? rr >> S::IB
                                     : ((rr & ((1u << S::RL) - 1u)) >> S::IB) + ((rr & ~((1u << S::RL) - 1u)) - (1u << S::RL));
-      rsp_st(Lr, resp ? popped : rr);                // (popped: entries down one, length - 1)
+      // (popped: entries down one, length - 1)
+      if constexpr (st_if_site(PXB_EV_SI_PROP))
+        rsp_st_if(Lr, popped, lanes(act) & lanes(in_mask0 != 0u) & lanes(pq_len <= PQ_CAP - 2u) & (SP ? lanes(true) : lanes(r != 0u)));
+      else rsp_st(Lr, resp ? popped : rr);
       const bool nnow = nkc ? ((nk & 7u) == (s4 & 7u)) : (((pn >> 26) & 15u) == s4);
       const bool rkeep = resp & (S::RH ? rr >= (1u << (2 * S::IB)) : S::RZ ? nk != 0u : rlen > 1u) & nnow;
       // (bit j is set whenever pin: clearing it is adding -1 << j)
@@ -1453,7 +1579,9 @@ struct EvLane : Src {
         if constexpr (LG) put(pw2, q, t_go ? Tn : (s_maj & (PDb == 0u)) ? 0u : CT);   // handleTick: c<id>.<Tn>
         const uint32_t k0o = ask ? ASK : o_maj ? PROPOSE : s_maj ? EXECUTE : NONE;
         if constexpr (draws_tap<Src>::value) Src::tap_prop(pin, q, r, rkind, px, py, pz, k0o, ask ? Tn : T, Tn, C2n, sPD);
-        broadcast(q, k0o, ask ? Tn : T, C2n, k0o != NONE, Tn, sPD, C2n);
+        // (sPD one compare at a time, for its lane mask)
+        broadcast(q, k0o, ask ? Tn : T, C2n, k0o != NONE, Tn, sPD, C2n, lanes(k0o != NONE),
+                  lanes(s_go) & lanes(maj1) & lanes(opaque(PDb) != 0u));
       }
     }
   }

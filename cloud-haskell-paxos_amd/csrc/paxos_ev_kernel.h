@@ -42,6 +42,51 @@ struct LdsMem {
   __host__ __device__ void sth(uint32_t base, uint32_t i, uint32_t v) const {
     reinterpret_cast<uint16_t*>(w + base * 64u)[i * 64u + lane] = (uint16_t)v;
   }
+  // Lane-masked stores (round 11): the store of the lanes whose predicate
+  // holds, without a branch and without the other lanes storing their old
+  // value back.  One statement: exec saved, ANDed with the predicate's lane
+  // mask (an AND: the iteration already runs with the wave's idle lanes masked
+  // off, and under wave-level branches), one vector LDS store, exec restored.
+  // The "memory" clobber keeps every LDS access on its side of the statement.
+  // The predicate is a lane mask (paxos_ev.h: lanes()).
+  // BASE: a compile-time word offset, the instruction's offset field (as LLVM
+  // folds it for a plain store; left in the address it cost a v_add per site).
+  // (The address is the word's LDS byte offset: LLVM folds the cast of the
+  // __shared__ array's generic pointer back to the array.)
+#if defined(__HIP_DEVICE_COMPILE__)
+  __device__ __forceinline__ uint32_t lds_off(const void* p) const {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+  }
+  template <uint32_t BASE = 0>
+  __device__ __forceinline__ void st_if(uint32_t i, uint32_t v, lanes_t c) const {
+    static_assert(BASE * 256u < 65536u, "ds offset field");
+    unsigned long long sv;
+    __asm__ volatile("s_and_saveexec_b64 %0, %1\n\tds_write_b32 %2, %3 offset:%4\n\ts_mov_b64 exec, %0"
+                     : "=&s"(sv) : "s"(c), "v"(lds_off(&w[i * 64u + lane])), "v"(v), "n"(BASE * 256u) : "memory", "scc");
+  }
+  template <uint32_t BASE>
+  __device__ __forceinline__ void st16_at_if(const uint16_t* p, uint32_t v, lanes_t c) const {
+    static_assert(BASE * 256u < 65536u, "ds offset field");
+    unsigned long long sv;
+    __asm__ volatile("s_and_saveexec_b64 %0, %1\n\tds_write_b16 %2, %3 offset:%4\n\ts_mov_b64 exec, %0"
+                     : "=&s"(sv) : "s"(c), "v"(lds_off(p)), "v"(v), "n"(BASE * 256u) : "memory", "scc");
+  }
+  template <uint32_t BASE = 0>
+  __device__ __forceinline__ void st16h_if(uint32_t i, uint32_t half, uint32_t v, lanes_t c) const {
+    st16_at_if<BASE>(&reinterpret_cast<const uint16_t*>(w)[(i * 64u + lane) * 2u + half], v, c);
+  }
+  template <uint32_t BASE = 0>
+  __device__ __forceinline__ void sth_if(uint32_t base, uint32_t i, uint32_t v, lanes_t c) const {
+    st16_at_if<BASE>(&reinterpret_cast<const uint16_t*>(w + base * 64u)[i * 64u + lane], v, c);
+  }
+#else
+  template <uint32_t BASE = 0>
+  void st_if(uint32_t i, uint32_t v, bool c) const { if (c) st(BASE + i, v); }
+  template <uint32_t BASE = 0>
+  void st16h_if(uint32_t i, uint32_t half, uint32_t v, bool c) const { if (c) st16h(BASE + i, half, v); }
+  template <uint32_t BASE = 0>
+  void sth_if(uint32_t base, uint32_t i, uint32_t v, bool c) const { if (c) sth(BASE + base, i, v); }
+#endif
   // OR into a word (ds_or_b32: no read-back on the critical path)
   __device__ void orw(uint32_t i, uint32_t v) const { atomicOr(&w[i * 64u + lane], v); }
 };

@@ -38,6 +38,10 @@ struct HostMem {
   uint32_t ldh(uint32_t base, uint32_t i) const { return ld16(base, i); }
   void sth(uint32_t base, uint32_t i, uint32_t v) const { st16(base, i, v); }
   void orw(uint32_t i, uint32_t v) const { w[i] |= v; }
+  // the lane-masked stores: on the host, the lane's own predicate
+  void st_if(uint32_t i, uint32_t v, bool c) const { if (c) st(i, v); }
+  void st16h_if(uint32_t i, uint32_t half, uint32_t v, bool c) const { if (c) st16h(i, half, v); }
+  void sth_if(uint32_t base, uint32_t i, uint32_t v, bool c) const { if (c) sth(base, i, v); }
 };
 
 constexpr int NB = 13;
