@@ -32,9 +32,13 @@ def draw(rng, kind):
     P = int(rng.integers(1, 3))
     N = int(rng.integers(2, 10))
     crash = int(rng.choice([0, rng.integers(1, 400000), 1000000]))
+    # (every kind but simple reaches the layouts of long runs, 0, 1 and 4 / 8:
+    # they also draw 2048 and ev::MAX_STEP_CAP, the longest run the per-lane
+    # kernels are eligible for, tests/ev_limits.py)
+    long_caps = [] if kind == "simple" else [2048, 4095]
     common = dict(seed=int(rng.integers(0, 1 << 63)), n_proposers=P, n_acceptors=N, crash_ppm=crash,
                   crash_len_max=int(rng.integers(1, 40)), crash_start_max=int(rng.integers(0, 30)),
-                  step_cap=int(rng.choice([int(rng.integers(1, 64)), 256, 300, 1024])))
+                  step_cap=int(rng.choice([int(rng.integers(1, 64)), 256, 300, 1024] + long_caps)))
     if kind == "simple":              # layout 6: no loss, no skew, delays <= 4
         return pxb.Config(loss_ppm=0, delay_max=int(rng.integers(1, 5)), skew_max=0, **common)
     if kind == "compact":             # compact 4- and 8-step layouts (loss and skew)
@@ -49,8 +53,9 @@ def draw(rng, kind):
         return pxb.Config(loss_ppm=int(rng.integers(0, 400000)), delay_max=int(rng.integers(1, 9)),
                           skew_max=int(rng.integers(0, 4)), **common)
     if kind == "log":                 # faulty log mode (the per-lane LG shape, delays <= 8)
+        # (up to 200 Ticks: byte reply seqs at their limit, logs past LOG_TRACK)
         return pxb.Config(loss_ppm=int(rng.integers(0, 200000)), delay_max=int(rng.integers(1, 9)),
-                          skew_max=int(rng.integers(0, 4)), n_ticks=int(rng.integers(2, 12)),
+                          skew_max=int(rng.integers(0, 4)), n_ticks=int(rng.choice([rng.integers(2, 12), rng.integers(12, 201)])),
                           tick_period=int(rng.integers(1, 16)), **common)
     return pxb.Config(loss_ppm=int(rng.integers(0, 1000001)), delay_max=int(rng.integers(1, 16)),
                       skew_max=int(rng.integers(0, 12)), **common)     # anything (general kernel too)
