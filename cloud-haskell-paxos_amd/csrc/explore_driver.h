@@ -15,7 +15,10 @@
 //     in front of and behind the candidate launch.
 //   explore_staged: the chunked host-buffer form around a device form given as
 //     a callable, with one optional per-parent column of the family's.
-// The kernels live in an unnamed namespace: each of the two units has its own.
+//   pxb_explore_win (paxos_explore_win.hip) has a minimal kernel and a device
+//     form of its own (two axes, 12 cells a parent) and takes the rest from
+//     here: explore_scratch, explore_list_tail, explore_staged_over.
+// The kernels live in an unnamed namespace: each of the including units has its own.
 // Included only where entry points are (hipCUB).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -203,12 +206,11 @@ inline int explore_scratch(int dev, uint64_t total, hipStream_t st, ExpScratch* 
   return PXB_OK;
 }
 
-// behind the candidate kernel on st: the minimal bits, counts and status, then the list
-inline hipError_t explore_list(const ExpList& l, const ExpScratch& s, uint64_t first_g, uint64_t* d_ids,
-                               uint64_t capacity, uint64_t* d_n_matches, hipStream_t st) {
+// behind a family's minimal kernel on st (which left the tiles' counts of the
+// listed bit `sel`): the list of the `total` candidates' flag bytes
+inline hipError_t explore_list_tail(uint64_t total, uint32_t sel, const ExpScratch& s, uint64_t first_g, uint64_t* d_ids,
+                                    uint64_t capacity, uint64_t* d_n_matches, hipStream_t st) {
   hipError_t err = hipSuccess;
-  hipLaunchKernelGGL(explore_minimal_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, l);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
   size_t scan_b = s.scan_b;
   err = hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, scan_b, widen_iter(s.tcount, Widen{}), s.toff, (int64_t)s.ntiles, st);
   if (err != hipSuccess) return err;
@@ -216,11 +218,18 @@ inline hipError_t explore_list(const ExpList& l, const ExpScratch& s, uint64_t f
                      s.list_base);
   if ((err = hipGetLastError()) != hipSuccess) return err;
   if (capacity) {
-    hipLaunchKernelGGL(explore_scatter_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, s.bytes, l.total, l.sel,
+    hipLaunchKernelGGL(explore_scatter_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, s.bytes, total, sel,
                        first_g, s.tcount, s.toff, s.list_base, d_ids, capacity);
     err = hipGetLastError();
   }
   return err;
+}
+// behind the candidate kernel on st: the minimal bits, counts and status, then the list
+inline hipError_t explore_list(const ExpList& l, const ExpScratch& s, uint64_t first_g, uint64_t* d_ids,
+                               uint64_t capacity, uint64_t* d_n_matches, hipStream_t st) {
+  hipLaunchKernelGGL(explore_minimal_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, l);
+  if (hipError_t err = hipGetLastError()) return err;
+  return explore_list_tail(l.total, l.sel, s, first_g, d_ids, capacity, d_n_matches, st);
 }
 
 inline hipError_t explore_no_hook(hipStream_t) { return hipSuccess; }
@@ -288,18 +297,20 @@ int explore_device(const ExpArgs& a, const Space* sp, const ExploreSpace& e, hip
 // chunk's device arguments `d`.  `extra` (nullable), of extra_elem bytes a
 // parent (0: the family has none): the family's own per-parent output column.
 // An output the caller did not ask for reaches the device form as null.
+// T: the candidates of a parent; cnt_words: the words of a parent's counts.
 template <class Call>
-int explore_staged(const ExpArgs& h, const ExploreSpace& e, void* extra, uint64_t extra_elem, const Call& call) {
+int explore_staged_over(const ExpArgs& h, uint64_t T, uint64_t cnt_words, void* extra, uint64_t extra_elem,
+                        const Call& call) {
   if (device_count() == 0) return PXB_E_NODEV;
   *h.n_matches = 0;
   if (h.count == 0) return PXB_OK;
   const uint64_t chunk = explore_chunk_hook();
-  const uint64_t per = chunk / e.T ? chunk / e.T : 1u, m_max = per < h.count ? per : h.count;
+  const uint64_t per = chunk / T ? chunk / T : 1u, m_max = per < h.count ? per : h.count;
   const uint64_t stride = script_stride(h.cfg->n_proposers, h.cfg->n_acceptors, h.depth);
-  const uint64_t cap = h.capacity < h.count * e.T ? h.capacity : h.count * e.T;
+  const uint64_t cap = h.capacity < h.count * T ? h.capacity : h.count * T;
   pxb::StagePlan plan;                            // rows (one chunk) | cursor | ids | counts | [extra] | status
   const pxb::StageRegion r_rows = plan.add(stride, m_max), r_n = plan.add(sizeof(uint64_t), 1);
-  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_cnt = plan.add(12u * sizeof(uint32_t), h.count);
+  const pxb::StageRegion r_ids = plan.add(sizeof(uint64_t), cap), r_cnt = plan.add(cnt_words * sizeof(uint32_t), h.count);
   const pxb::StageRegion r_x = plan.add(extra_elem, h.count), r_st = plan.add(sizeof(uint32_t), h.count);
   Staging S(plan);
   S.zero(r_n);
@@ -310,7 +321,7 @@ int explore_staged(const ExpArgs& h, const ExploreSpace& e, void* extra, uint64_
     const uint64_t m = h.count - a < m_max ? h.count - a : m_max;
     S.up(r_rows, h.rows + a * stride, m);
     const ExpArgs d{h.cfg, S.ptr<uint8_t>(r_rows), m, h.depth, a, S.ptr<uint64_t>(r_ids), cap, S.ptr<uint64_t>(r_n),
-                    d_cnt ? d_cnt + a * 12u : nullptr, d_st ? d_st + a : nullptr};
+                    d_cnt ? d_cnt + a * cnt_words : nullptr, d_st ? d_st + a : nullptr};
     if (S.ok()) S.note(call(d, d_x ? d_x + a * extra_elem : nullptr));
     // (the next chunk's rows overwrite these: wait for the kernels that read them)
     if (S.ok()) S.note(hipStreamSynchronize(nullptr));
@@ -321,6 +332,11 @@ int explore_staged(const ExpArgs& h, const ExploreSpace& e, void* extra, uint64_
   S.down(r_x, extra, h.count);
   S.down(r_st, h.status, h.count);
   return S.finish();
+}
+// (the link-only families: T of the space, 4 x 3 counts a parent)
+template <class Call>
+int explore_staged(const ExpArgs& h, const ExploreSpace& e, void* extra, uint64_t extra_elem, const Call& call) {
+  return explore_staged_over(h, e.T, 12u, extra, extra_elem, call);
 }
 
 }  // namespace

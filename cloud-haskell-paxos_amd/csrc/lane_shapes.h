@@ -1,7 +1,7 @@
 // lane_shapes.h — the shapes the lane kernels exist in, once.  pxb_trace_instance
-// (paxos_trace.hip), the eight families built as one unit per proposer count
+// (paxos_trace.hip), the nine families built as one unit per proposer count
 // (paxos_trace_batch, paxos_script, paxos_shrink, paxos_explore, paxos_events,
-// paxos_cover, paxos_explore_cover and paxos_shrink_cover .hip) and the host
+// paxos_cover, paxos_explore_cover, paxos_explore_win and paxos_shrink_cover .hip) and the host
 // builds of their lanes (tests/native/host_lane.h) all pick an instantiation
 // here.
 //

@@ -1980,6 +1980,320 @@ def explore_cover_device(cfg: Config, d_rows, count: int, depth: int, site_depth
                                           _ptr(d_counts), _ptr(d_reach), _ptr(d_status), s))
 
 
+# ---- isolation windows as sites of the exploration (include/paxos_batch.h, docs/SEMANTICS.md §17) ----
+EXPLORE_WIN_MAX_RADIUS = 2
+EXPLORE_WIN_OPEN = 2             # pxb_explore_win_space.flags: one more length alternative, "to the end"
+WIN_END = 4096                   # c1 of the open alternative
+
+
+class pxb_explore_win_space(C.Structure):
+    _fields_ = [("site_depth", C.c_uint32), ("radius", C.c_uint32), ("flag_mask", C.c_uint32), ("flags", C.c_uint32),
+                ("q", pxb_cover_query), ("win_radius", C.c_uint32), ("win_first", C.c_uint32),
+                ("win_starts", C.c_uint32), ("win_lens", C.c_uint32)]
+
+
+class pxb_explore_win_reach(C.Structure):
+    _fields_ = [("count", ((C.c_uint32 * 32) * 4) * 3), ("first", ((C.c_uint32 * 32) * 4) * 3),
+                ("parent_mask", C.c_uint32), ("union_mask", C.c_uint32)]
+
+
+EXPLORE_WIN_REACH_BYTES = 3080
+assert C.sizeof(pxb_explore_win_reach) == EXPLORE_WIN_REACH_BYTES and C.sizeof(pxb_explore_win_space) == 48
+
+
+@dataclasses.dataclass(frozen=True)
+class WinGrid:
+    """The window alternatives of an acceptor: starts first .. first + starts -
+    1, lengths 1 .. lens and, with `open`, one more that lasts to the end (c1 =
+    4096); `radius`: how many acceptors' windows a candidate may replace (0..2).
+    Digit d is start d // L and length index d % L, L = lens + open."""
+    first: int
+    starts: int
+    lens: int
+    open: bool = False
+    radius: int = 1
+
+    @property
+    def L(self) -> int:
+        return self.lens + (1 if self.open else 0)
+
+    @property
+    def W(self) -> int:
+        return self.starts * self.L
+
+    def valid(self) -> bool:
+        return (0 <= self.radius <= EXPLORE_WIN_MAX_RADIUS and self.starts >= 1 and self.first >= 0 and self.lens >= 0
+                and self.L >= 1 and self.first + self.starts - 1 + self.lens <= WIN_END)
+
+    def window(self, d: int):
+        """(c0, c1) of digit d."""
+        i, j = divmod(d, self.L)
+        c0 = self.first + i
+        return c0, (c0 + 1 + j if j < self.lens else WIN_END)
+
+
+def _win_bases(N: int, W: int, radius: int):
+    """[base_0, .., base_(radius + 1)] of the window choices: base_r = sum of
+    C(N, q) W^q over q < r; the last is H."""
+    import math
+    base = [0]
+    for r in range(radius + 1):
+        base.append(base[-1] + math.comb(N, r) * W ** r)
+    return base
+
+
+def _win_split(cfg, site_depth, radius, grid):
+    """(T, H) of a valid joint space, or (0, 0)."""
+    T = explore_total(cfg, site_depth, radius)
+    if not T or not grid.valid():
+        return 0, 0
+    H = _win_bases(cfg.n_acceptors, grid.W, grid.radius)[-1]
+    return (T, H) if H * T <= EXPLORE_MAX_TOTAL else (0, 0)
+
+
+def explore_win_total(cfg: Config, site_depth: int, radius: int, grid: WinGrid) -> int:
+    """pxb_explore_win_total: T_w = H T candidates per parent, or 0 for a space
+    that is invalid or larger than 2^30."""
+    T, H = _win_split(cfg, site_depth, radius, grid)
+    return T * H
+
+
+def _win_unrank_many(N: int, grid: WinGrid, h):
+    """The window choices h as arrays: (r (n,), acceptors (n, 2), digits (n, 2)),
+    unused columns 0.  §12's order over N sites with W alternatives."""
+    import numpy as np
+    h = np.asarray(h, dtype=np.int64)
+    W = grid.W
+    base = np.array(_win_bases(N, W, grid.radius) + [0, 0], dtype=np.int64)
+    H = int(base[grid.radius + 1])
+    if len(h) and (h.min() < 0 or h.max() >= H):
+        raise ValueError("h: 0..%d" % (H - 1))
+    r = np.zeros(len(h), dtype=np.int64)
+    for q in range(1, grid.radius + 1):
+        r[h >= base[q]] = q
+    x = h - base[r]
+    acc, dig = np.zeros((len(h), 2), dtype=np.int64), np.zeros((len(h), 2), dtype=np.int64)
+    one, two = r == 1, r == 2
+    acc[one, 0], dig[one, 0] = x[one] // W, x[one] % W
+    m, v = x[two] // (W * W), x[two] % (W * W)
+    s = np.arange(10, dtype=np.int64)
+    a2 = np.searchsorted(s * (s - 1) // 2, m, side="right") - 1      # the largest s with C(s, 2) <= m
+    acc[two, 1], acc[two, 0] = a2, m - a2 * (a2 - 1) // 2
+    dig[two, 0], dig[two, 1] = v % W, v // W
+    return r, acc, dig
+
+
+def explore_win_unrank(cfg: Config, site_depth: int, radius: int, grid: WinGrid, c: int):
+    """Candidate c (c' = h T + c of §17) as ((acceptors, window digits), (sites,
+    link digits)): the window choice h = c // T in §12's order over N acceptors
+    with W alternatives, and explore_unrank of the link part c % T."""
+    T, H = _win_split(cfg, site_depth, radius, grid)
+    if not T:
+        raise ValueError("no such space (or more than 2^30 candidates)")
+    if not 0 <= c < T * H:
+        raise ValueError("c: 0..%d" % (T * H - 1))
+    r, acc, dig = _win_unrank_many(cfg.n_acceptors, grid, [c // T])
+    q = int(r[0])
+    links = explore_unrank(2 * cfg.n_proposers * cfg.n_acceptors * site_depth, cfg.delay_max, radius, c % T)
+    return ([int(a) for a in acc[0, :q]], [int(d) for d in dig[0, :q]]), links
+
+
+def explore_win_changes(cfg: Config, site_depth: int, radius: int, grid: WinGrid, c: int):
+    """The changes of candidate c: ([(a, c0, c1)] in ascending acceptor order,
+    explore_changes' [(dirn, p, a, k, digit)] of the link part)."""
+    (accs, digs), _ = explore_win_unrank(cfg, site_depth, radius, grid, c)
+    T = explore_total(cfg, site_depth, radius)
+    return [(a, *grid.window(d)) for a, d in zip(accs, digs)], explore_changes(cfg, site_depth, radius, c % T)
+
+
+def _explore_win_split_ids(cfg, parents, depth, site_depth, radius, grid, ids):
+    import numpy as np
+    parents = _script_rows(cfg, parents, depth)
+    T, H = _win_split(cfg, site_depth, radius, grid)
+    if not T:
+        raise ValueError("no such space (or more than 2^30 candidates)")
+    ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1).astype(np.int64)
+    i, cw = ids // (T * H), ids % (T * H)
+    if len(ids) and i.max() >= len(parents):
+        raise ValueError("ids: beyond the last parent")
+    return parents, T, i, cw // T, cw % T
+
+
+def explore_win_skipped(cfg: Config, parents, depth: int, site_depth: int, radius: int, grid: WinGrid, ids):
+    """bool (n,): the candidates whose link part changes a keep site of their
+    parent (explore_skipped).  A changed window never skips."""
+    parents, T, i, h, c = _explore_win_split_ids(cfg, parents, depth, site_depth, radius, grid, ids)
+    return explore_skipped(cfg, parents, depth, site_depth, radius, i * T + c)
+
+
+def explore_win_rows(cfg: Config, parents, depth: int, site_depth: int, radius: int, grid: WinGrid, ids):
+    """The candidates `ids` (global: parent index * T_w + c', as explore_win
+    lists them) materialised: uint8 (len(ids), stride), what pxb_explore_win_row
+    writes: explore_rows of the link part, and the changed acceptors' windows as
+    explicit (c0, c1) pairs in place of whatever the parent has there."""
+    import numpy as np
+    parents, T, i, h, c = _explore_win_split_ids(cfg, parents, depth, site_depth, radius, grid, ids)
+    rows = explore_rows(cfg, parents, depth, site_depth, radius, i * T + c)
+    r, acc, dig = _win_unrank_many(cfg.n_acceptors, grid, h)
+    win = script_windows(cfg, rows)
+    st, j = dig // grid.L, dig % grid.L
+    c0 = grid.first + st
+    c1 = np.where(j < grid.lens, c0 + 1 + j, WIN_END)
+    for q in range(2):
+        w = np.nonzero(r > q)[0]
+        win[w, acc[w, q], 0], win[w, acc[w, q], 1] = c0[w, q], c1[w, q]
+    return rows
+
+
+def win_reach_dtype():
+    """A pxb_explore_win_reach as a numpy structured dtype (3,080 bytes)."""
+    import numpy as np
+    return np.dtype([("count", np.uint32, (3, 4, 32)), ("first", np.uint32, (3, 4, 32)), ("parent_mask", np.uint32),
+                     ("union_mask", np.uint32)])
+
+
+@dataclasses.dataclass
+class ExploreWinReach:
+    """pxb_explore_win_reach as Python values: counts[r_w][r_l][b], the
+    candidates of the cell that ran OK and have class b; first[r_w][r_l][b], the
+    lowest such c' or REACH_NONE; parent_mask, candidate 0's mask; union, the
+    classes with any count.  `tail_ok`: the words at b >= COVER_CLASSES are
+    zero counts and REACH_NONE firsts."""
+    counts: list
+    first: list
+    parent_mask: int
+    union: int
+    tail_ok: bool
+
+    @classmethod
+    def from_record(cls, rec):
+        cnt, fst = rec["count"], rec["first"]
+        n = COVER_CLASSES
+        return cls([[[int(x) for x in cnt[a][b][:n]] for b in range(4)] for a in range(3)],
+                   [[[int(x) for x in fst[a][b][:n]] for b in range(4)] for a in range(3)],
+                   int(rec["parent_mask"]), int(rec["union_mask"]),
+                   bool((cnt[:, :, n:] == 0).all() and (fst[:, :, n:] == REACH_NONE).all()))
+
+    def by_name(self):
+        """{class name: {(r_w, r_l): (first, count)}} of the reached classes, the populated cells only."""
+        return {name: {(a, b): (self.first[a][b][k], self.counts[a][b][k]) for a in range(3) for b in range(4)
+                       if self.counts[a][b][k]}
+                for k, name in enumerate(COVER_NAMES) if (self.union >> k) & 1}
+
+
+def explore_win_reach_of(masks, ran, r_w, r_l):
+    """The reach record of ONE parent from its T_w candidates' coverage masks,
+    "ran OK" bits and radii (arrays over c'), in numpy: the specification of
+    docs/SEMANTICS.md §17.  Returns a 0-d array of win_reach_dtype()."""
+    import numpy as np
+    masks = np.where(np.asarray(ran, dtype=bool), np.asarray(masks, dtype=np.uint32), np.uint32(0))
+    r_w, r_l = np.asarray(r_w), np.asarray(r_l)
+    if not masks.shape == r_w.shape == r_l.shape or masks.ndim != 1:
+        raise ValueError("masks, ran, r_w, r_l: one per candidate")
+    rec = np.zeros((), dtype=win_reach_dtype())
+    rec["first"][:] = REACH_NONE
+    for b in range(COVER_CLASSES):
+        has = ((masks >> np.uint32(b)) & np.uint32(1)) != 0
+        for a in range(3):
+            for l in range(4):
+                w = np.nonzero(has & (r_w == a) & (r_l == l))[0]
+                if len(w):
+                    rec["count"][a, l, b], rec["first"][a, l, b] = len(w), int(w[0])
+                    rec["union_mask"] |= np.uint32(1 << b)
+    rec["parent_mask"] = masks[0]
+    return rec
+
+
+def reach_distance_win(reach):
+    """The reach distance of every class from a record (an ExploreWinReach or a
+    win_reach_dtype() record): a list of COVER_CLASSES entries, the least r_w +
+    r_l of a cell with a non-zero count, or None."""
+    if not isinstance(reach, ExploreWinReach):
+        reach = ExploreWinReach.from_record(reach)
+    return [min((a + l for a in range(3) for l in range(4) if reach.counts[a][l][b]), default=None)
+            for b in range(COVER_CLASSES)]
+
+
+def _explore_win_space(site_depth, radius, grid, query, flag_mask, minimal):
+    q = query.to_c() if query is not None else pxb_cover_query(0, 0, 0, 0)
+    flags = (EXPLORE_MINIMAL if minimal else 0) | (EXPLORE_WIN_OPEN if grid.open else 0)
+    return pxb_explore_win_space(site_depth, radius, flag_mask, flags, q, grid.radius, grid.first, grid.starts, grid.lens)
+
+
+_WIN_ARGS = {"pxb_explore_win_row": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p],
+             "pxb_explore_win_device": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_uint64] + [C.c_void_p] * 5,
+             "pxb_explore_win": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64] +
+                                [C.c_void_p] * 4}
+
+
+def _win_fn(name):
+    """An entry point of this family, found by symbol: a library without it is an error."""
+    lib = load()
+    try:
+        fn = getattr(lib, name)
+    except AttributeError:
+        raise PaxosError("libpaxos_batch.so has no %s — rebuild it" % name)
+    if name == "pxb_explore_win_total":
+        fn.argtypes, fn.restype = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p], C.c_uint64
+    else:
+        fn.argtypes, fn.restype = _WIN_ARGS[name], C.c_int
+    return fn
+
+
+def explore_win(cfg: Config, parents, depth: int, site_depth: int, radius: int, grid: WinGrid,
+                query: Optional[CoverQuery] = None, flag_mask: int = 0, minimal: bool = True, capacity=None):
+    """pxb_explore_win: explore_cover over link changes AND isolation windows.  A
+    candidate changes at most `radius` link entries and replaces the window of
+    at most grid.radius acceptors by one of the grid's.  Returns (ids,
+    n_matches, counts uint32 (n, 3, 4, 3), reach, status): ids as parent index *
+    T_w + c' ascending; counts[i, r_w, r_l] = (ran OK, held, minimal); reach a
+    list of ExploreWinReach; reach_distance_win(reach[i]) says how many changes
+    (windows plus link entries) away from parent i each handler class lies."""
+    import numpy as np
+    fn = _win_fn("pxb_explore_win")
+    rows = _script_rows(cfg, parents, depth)
+    n = len(rows)
+    counts = np.zeros((n, 3, 4, 3), dtype=np.uint32)
+    status = np.zeros(n, dtype=np.uint32)
+    reach = np.zeros(n, dtype=win_reach_dtype())
+    c = cfg.to_c(0, 1)
+    sp = _explore_win_space(site_depth, radius, grid, query, flag_mask, minimal)
+    nm = C.c_uint64(0)
+    head = (C.byref(c), _ptr(rows) if n else None, n, depth, C.byref(sp))
+    tail = (C.byref(nm), _ptr(counts) if n else None, _ptr(reach) if n else None, _ptr(status) if n else None)
+    ids = _explore_two_call(lambda p, cap: check(fn(*head, p, cap, *tail)), nm, capacity)
+    return ids, nm.value, counts, [ExploreWinReach.from_record(r) for r in reach], status
+
+
+def explore_win_device(cfg: Config, d_rows, count: int, depth: int, site_depth: int, radius: int, grid: WinGrid,
+                       d_n_matches, query: Optional[CoverQuery] = None, flag_mask: int = 0, d_ids=None,
+                       capacity: int = 0, d_counts=None, d_reach=None, d_status=None, first_parent: int = 0,
+                       minimal: bool = True, stream=None):
+    """pxb_explore_win_device on torch tensors, asynchronous on `stream`, no
+    synchronisation: the buffers of explore_cover_device with d_counts int32
+    (count, 3, 4, 3) and d_reach uint8 (count * 3080,) (8-byte aligned; after a
+    synchronise, d_reach.cpu().numpy().view(win_reach_dtype()) gives the
+    records).  Sizes and dtypes are checked here."""
+    if d_n_matches is None:
+        raise ValueError("d_n_matches is required")
+    if capacity and d_ids is None:
+        raise ValueError("d_ids is required when capacity > 0")
+    _check_script_call(cfg, d_rows, count, depth)
+    _check_buf("d_n_matches", d_n_matches, 1, 8)
+    _check_buf("d_ids", d_ids, capacity, 8)
+    _check_buf("d_counts", d_counts, 36 * count, 4)
+    _check_buf("d_status", d_status, count, 4)
+    if d_reach is not None:
+        _check_bytes("d_reach", d_reach, EXPLORE_WIN_REACH_BYTES * count)
+    c = cfg.to_c(0, 1)
+    sp = _explore_win_space(site_depth, radius, grid, query, flag_mask, minimal)
+    s = C.c_void_p(stream) if stream else None
+    check(_win_fn("pxb_explore_win_device")(C.byref(c), _ptr(d_rows), count, depth, C.byref(sp), first_parent,
+                                            _ptr(d_ids) if capacity else None, capacity, _ptr(d_n_matches),
+                                            _ptr(d_counts), _ptr(d_reach), _ptr(d_status), s))
+
+
 def init(n_devices: int = 0):
     """pxb_init: allocate the per-device scratch of devices 0..n-1 up front."""
     check(load().pxb_init(n_devices))

@@ -930,6 +930,80 @@ int pxb_explore_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count
                       const pxb_explore_cover_space* space, uint64_t* ids, uint64_t capacity,
                       uint64_t* n_matches, uint32_t* counts, pxb_explore_reach* reach, uint32_t* status);
 
+/* ---- isolation windows as sites of the exploration (additive to ABI 5, found by symbol) ---
+ * pxb_explore_cover over a larger space (docs/SEMANTICS.md §17): a candidate
+ * changes at most `radius` link entries AND replaces the isolation window of at
+ * most `win_radius` acceptors.  The LINK PART is pxb_explore's space unchanged
+ * (S, A, T, the order, the digits, the skipped candidates, a bad parent); c is
+ * one of its candidates, 0 <= c < T.  The WINDOW PART: with L = win_lens + (flags
+ * & PXB_EXPLORE_WIN_OPEN ? 1 : 0) an acceptor has W = win_starts L alternatives;
+ * digit d is start i = d / L and length index j = d % L: the window [c0, c1)
+ * with c0 = win_first + i and c1 = c0 + 1 + j for j < win_lens, 4096 for the
+ * open one.  With N = cfg->n_acceptors there are H = sum over q <= win_radius of
+ * C(N, q) W^q WINDOW CHOICES, ordered as pxb_explore orders candidates over N
+ * sites with W alternatives: by window radius, by the acceptors' combination
+ * (a_1 < a_2, rank C(a_1, 1) + C(a_2, 2)), then by the digits, a_1's the least
+ * significant.  Choice 0 leaves the parent's windows alone; a changed
+ * acceptor's window REPLACES what the parent has there (explicit, none or the
+ * 0xFFFF keep pair) and is never skipped.  CANDIDATE c' = h T + c, T_w = H T per
+ * parent; its pair of radii is (r_w, r_l), its distance r_w + r_l.  Ran OK, the
+ * mask and the predicate are pxb_explore_cover's.  A held candidate is MINIMAL
+ * when no other candidate made of a subset of its window changes and a subset
+ * of its link changes (same digits, the empty subsets included) holds.          */
+#define PXB_EXPLORE_WIN_MAX_RADIUS 2u
+#define PXB_EXPLORE_WIN_OPEN       2u   /* flags: one more length alternative, "to the end" (c1 = 4096) */
+typedef struct pxb_explore_win_space {   /* 48 B, no implicit padding */
+  uint32_t site_depth;              /* 1..depth                                    */
+  uint32_t radius;                  /* 0..PXB_EXPLORE_MAX_RADIUS                   */
+  uint32_t flag_mask;               /* PXB_F_* bits of the predicate; 0: no outcome condition */
+  uint32_t flags;                   /* PXB_EXPLORE_MINIMAL | PXB_EXPLORE_WIN_OPEN  */
+  pxb_cover_query q;                /* reserved must be 0                          */
+  uint32_t win_radius;              /* 0..2 acceptors whose window a candidate replaces */
+  uint32_t win_first;               /* first start step                            */
+  uint32_t win_starts;              /* >= 1: starts win_first .. win_first + win_starts - 1 */
+  uint32_t win_lens;                /* lengths 1..win_lens (may be 0 only with WIN_OPEN);
+                                       win_first + win_starts - 1 + win_lens <= 4096 */
+} pxb_explore_win_space;
+typedef struct pxb_explore_win_reach {   /* 3080 B, no implicit padding */
+  uint32_t count[3][4][32];         /* [r_w][r_l][b]: candidates of the cell that ran OK and have class b */
+  uint32_t first[3][4][32];         /* the lowest c' (< T_w) of the cell with class b; 0xFFFFFFFF when none, and for b >= 29 */
+  uint32_t parent_mask;             /* candidate 0's mask (0 if it did not run OK) */
+  uint32_t union_mask;              /* the classes with any non-zero count */
+} pxb_explore_win_reach;
+
+/* T_w, or 0 for a space that is invalid or larger than 2^30 candidates
+ * (flag_mask, q and PXB_EXPLORE_MINIMAL are not read).                        */
+uint64_t pxb_explore_win_total(uint32_t n_proposers, uint32_t n_acceptors, uint32_t delay_max,
+                               const pxb_explore_win_space* space);
+/* pxb_explore_win_row: candidate c (c' above, < T_w) of `parent`, materialised
+ * into out_row as pxb_explore_row does: the changed link bytes, and the
+ * changed acceptors' windows as explicit (c0, c1) pairs.  Host only, pure.
+ * PXB_E_INVAL for c >= T_w, a changed keep site of a link and an invalid space. */
+int pxb_explore_win_row(const pxb_config* cfg, uint32_t depth, const pxb_explore_win_space* space,
+                        const uint8_t* parent, uint64_t c, uint8_t* out_row);
+/* pxb_explore_win_device: DEVICE buffers, asynchronous on `stream`, no device
+ * synchronisation.  Ids (g = (first_parent + i) T_w + c', ascending), cursor,
+ * capacity and d_status exactly as pxb_explore_cover_device.
+ *   d_counts (nullable)  count x 3 x 4 x 3 uint32, OVERWRITTEN: [r_w][r_l]{ran OK,
+ *                        held, minimal}.
+ *   d_reach (nullable, 8-byte aligned)  `count` records, OVERWRITTEN; integer
+ *                        adds and minima only: independent of the launch order
+ *                        and of the host form's chunking.
+ * No candidate row is ever stored.  Scratch as pxb_explore_device.  PXB_E_INVAL
+ * for everything pxb_explore_cover_device refuses (with T_w in T's place and
+ * PXB_EXPLORE_WIN_OPEN a known flag), and for win_starts == 0, win_radius > 2,
+ * win_lens == 0 without WIN_OPEN, the 4096 bound above and T_w > 2^30.         */
+int pxb_explore_win_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
+                           const pxb_explore_win_space* space, uint64_t first_parent,
+                           uint64_t* d_ids, uint64_t capacity, uint64_t* d_n_matches,
+                           uint32_t* d_counts, pxb_explore_win_reach* d_reach, uint32_t* d_status, void* stream);
+/* pxb_explore_win: HOST buffers, blocking, on the current device; PXB_E_NODEV
+ * without a GPU (checked after the validation).  Chunked as pxb_explore (whole
+ * parents per PXB_EXPLORE_CHUNK); no output depends on it.                     */
+int pxb_explore_win(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
+                    const pxb_explore_win_space* space, uint64_t* ids, uint64_t capacity,
+                    uint64_t* n_matches, uint32_t* counts, pxb_explore_win_reach* reach, uint32_t* status);
+
 /* ---- shrinking over a coverage predicate (additive to ABI 5, found by symbol) ---
  * pxb_shrink_batch with one change, the PREDICATE of a run (docs/SEMANTICS.md
  * §16): status PXB_TRACE_OK; flag_mask == 0 or result.flags & 0xFF & flag_mask
