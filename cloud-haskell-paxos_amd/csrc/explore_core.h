@@ -17,8 +17,9 @@
 //
 // Here: the space's sizes, unrank and rank, the byte accessor a candidate's lane
 // reads its parent's row through (no candidate row exists anywhere), the
-// keep-site and bad-parent tests, the lane's draw source and start, and the
-// minimality test over the candidates' flag bytes.
+// keep-site and bad-parent tests, the lane's draw source and start, the
+// minimality test over the candidates' flag bytes, and the space's policy for
+// the shared driver (ExploreLinkX).
 #pragma once
 #include <stdint.h>
 
@@ -224,6 +225,45 @@ __host__ __device__ __forceinline__ bool explore_is_minimal(const ExploreSpace& 
   for (uint32_t sub = 0u; sub < full; ++sub) any |= (bytes[explore_rank_subset(e, k, sub)] & EXP_HELD) != 0u;
   return !any;
 }
+
+// ---- the space policy of the link space ----
+// What explore_driver.h, the reach reduction (explore_reach.h) and the host
+// programs (tests/native/explore_host.h) ask of a space: candidate g (< 2^32)
+// of a call is candidate cw (< total) of parent i, which is a window choice h
+// with a link candidate c; it lies in one of CELLS cells, and is counted in a
+// reach record per cell.  Here h = 0 always; explore_win_core.h's ExploreWinX
+// is the joint space's.
+struct ExploreSplit {
+  uint32_t i, cw, h, c;
+};
+struct ExploreLinkX {
+  typedef ExploreSpace Space;
+  typedef pxb_explore_reach Reach;
+  static constexpr uint32_t CELLS = 4u;                            // radii
+  static constexpr uint32_t COUNT_WORDS = CELLS * 32u, FIRST_WORDS = 32u;   // of Reach, in front of its two masks
+  static constexpr uint32_t FLAGS = PXB_EXPLORE_MINIMAL;           // what the space struct's flags may hold
+  __host__ __device__ static __forceinline__ uint64_t total(const Space& e) { return e.T; }
+  __host__ __device__ static __forceinline__ const ExploreSpace& links(const Space& e) { return e; }
+  __host__ __device__ static __forceinline__ ExploreSplit split(const Space& e, uint32_t g) {
+    const uint32_t tt = (uint32_t)e.T, i = g / tt, c = g - i * tt;
+    return ExploreSplit{i, c, 0u, c};
+  }
+  __host__ __device__ static __forceinline__ uint32_t cell(const Space& e, uint32_t, uint32_t c) {
+    return explore_radius(e, c);
+  }
+  // (`bytes`: the parent's `total` flag bytes)
+  __host__ __device__ static __forceinline__ bool is_minimal(const Space& e, uint32_t, uint32_t c, const uint8_t* bytes) {
+    return explore_is_minimal(e, explore_unrank(e, c), bytes);
+  }
+  __host__ __device__ static __forceinline__ uint32_t* count(Reach* o, uint32_t cell) {
+    return &o->count[0][0] + cell * 32u;
+  }
+  __host__ __device__ static __forceinline__ uint32_t* first(Reach* o, uint32_t) { return &o->first[0]; }
+  // behind the begin: nothing
+  template <class Lane>
+  __host__ __device__ static __forceinline__ void apply(Lane&, const Space&, uint32_t) {}
+};
+static_assert(sizeof(pxb_explore_reach) == (ExploreLinkX::COUNT_WORDS + ExploreLinkX::FIRST_WORDS + 2u) * 4u, "Reach words");
 
 }  // namespace ev
 }  // namespace pxb

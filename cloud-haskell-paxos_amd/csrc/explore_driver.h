@@ -1,27 +1,29 @@
-// explore_driver.h — the explorer's driver (include/paxos_batch.h,
-// docs/SEMANTICS.md §12, §15): what pxb_explore (paxos_explore.hip) and
-// pxb_explore_cover (paxos_explore_cover.hip) share around their candidate
-// kernels, as shrink_driver.h is the shrinkers'.
+// explore_driver.h — the explorers' driver (include/paxos_batch.h,
+// docs/SEMANTICS.md §12, §15, §17): what pxb_explore (paxos_explore.hip),
+// pxb_explore_cover (paxos_explore_cover.hip) and pxb_explore_win
+// (paxos_explore_win.hip) share around their candidate kernels, as
+// shrink_driver.h is the shrinkers'.  Everything is over a space policy X
+// (explore_core.h: ExploreLinkX; explore_win_core.h: ExploreWinX): the
+// candidates of a parent, their split, their cell, the minimality rule.
 //   What follows the candidate kernel, over the candidates' flag bytes: the
-//     minimal kernel with the per-(parent, radius) counts and the status,
+//     minimal kernel with the per-(parent, cell) counts and the status,
 //     hipCUB's exclusive sum over the tiles, the cursor kernel and the scatter
 //     kernel.
-//   explore_validate: the argument rules of every exploring call (a family's
-//     own rules, and the kernel of the shape, stay with the family).
-//   explore_device: the device form after validation.  Parameterised by the
-//     candidate launch: the kernel, and its parameter struct, of which the
+//   explore_validate<X>: the argument rules of every exploring call, the bits
+//     the space's flags may hold among them (a family's own rules, how its
+//     space is made, and the kernel of the shape, stay with the family).
+//   explore_device<X>: the one device form after validation.  Parameterised by
+//     the candidate launch: the kernel, and its parameter struct, of which the
 //     family has set its own fields and the driver fills those every such
-//     struct has under the same names; and by two hooks that may queue kernels
-//     in front of and behind the candidate launch.
-//   explore_staged: the chunked host-buffer form around a device form given as
-//     a callable, with one optional per-parent column of the family's.
-//   pxb_explore_win (paxos_explore_win.hip) has a minimal kernel and a device
-//     form of its own (two axes, 12 cells a parent) and takes the rest from
-//     here: explore_scratch, explore_list_tail, explore_staged_over.
+//     struct has under the same names; and by hooks that may queue kernels in
+//     front of and behind the candidate launch and test a column's alignment.
+//   explore_staged<X>: the chunked host-buffer form around a device form given
+//     as a callable, with one optional per-parent column of the family's.
 // The kernels live in an unnamed namespace: each of the including units has its own.
 // Included only where entry points are (hipCUB).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "../../include/paxos_batch.h"
 #include "explore_core.h"
@@ -38,8 +40,9 @@ constexpr int XBLOCK = 256;                       // candidates per tile of the 
 constexpr int XWAVES = XBLOCK / 64;
 constexpr uint64_t MAX_CALL = 1ull << 32;         // candidates of one device call
 
+template <class X>
 struct ExpList {
-  ExploreSpace e;
+  typename X::Space x;
   const uint8_t* rows;
   uint64_t stride;
   uint64_t total;
@@ -47,7 +50,7 @@ struct ExpList {
   uint32_t sel;                     // the listed bit: EXP_MINIMAL or EXP_HELD
   uint8_t* bytes;
   uint32_t* tcount;                 // listed candidates per tile
-  uint32_t* counts;                 // count * 4 * 3, zeroed (nullable)
+  uint32_t* counts;                 // count * X::CELLS * 3, zeroed (nullable)
   uint32_t* status;                 // count (nullable)
 };
 
@@ -61,26 +64,28 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t wave_value, uint32_t* s_w
   return t;
 }
 
-__global__ __launch_bounds__(XBLOCK) void explore_minimal_kernel(ExpList k) {
+template <class X>
+__global__ __launch_bounds__(XBLOCK) void explore_minimal_kernel(ExpList<X> k) {
   __shared__ uint32_t s_w[XWAVES];
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t g = (uint64_t)blockIdx.x * XBLOCK + threadIdx.x;
   const bool in = g < k.total;
   uint32_t f = 0u, key = 0u;
   if (in) {
-    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
-    key = i * 4u + explore_radius(k.e, c);
+    const ExploreSplit s = X::split(k.x, (uint32_t)g);   // (g < 2^32)
+    const uint32_t i = s.i;
+    key = i * X::CELLS + X::cell(k.x, s.h, s.c);
     f = k.bytes[g];
     // (the other candidates' held bits are final: this kernel only ever adds the minimal bit)
-    if ((f & EXP_HELD) && explore_is_minimal(k.e, explore_unrank(k.e, c), k.bytes + (uint64_t)i * tt)) {
+    if ((f & EXP_HELD) && X::is_minimal(k.x, s.h, s.c, k.bytes + (uint64_t)i * (uint32_t)X::total(k.x))) {
       f |= EXP_MINIMAL;
       k.bytes[g] = (uint8_t)f;
     }
-    if (c == 0u && k.status)
+    if (s.cw == 0u && k.status)
       k.status[i] = explore_parent_bad(k.rows + (uint64_t)i * k.stride, k.P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
   }
   if (k.counts) {
-    // {ran OK, held, minimal} per (parent, radius): one add per distinct key of the wave and column
+    // {ran OK, held, minimal} per (parent, cell): one add per distinct key of the wave and column
     unsigned long long act = __ballot(f != 0u);
     while (act != 0ull) {                         // (wave-uniform)
       const int lead = __ffsll(act) - 1;
@@ -150,6 +155,19 @@ inline int validate_space_of(const pxb_config* cfg, uint32_t depth, uint32_t sit
   *e = space_of(cfg, site_depth, radius);
   return e->T ? PXB_OK : PXB_E_INVAL;
 }
+// the *_row entry points' link part: out_row (which may be `parent`) = the
+// parent's row with the links of link candidate c (< e.T) rewritten
+inline int explore_row_links(const pxb_config* cfg, uint32_t depth, uint32_t site_depth, const ExploreSpace& e,
+                             const uint8_t* parent, uint64_t c, uint8_t* out_row) {
+  const uint32_t N = cfg->n_acceptors;
+  const ExploreByte x = explore_byte(e, explore_unrank(e, c), parent, N, site_depth, depth);
+  if (explore_changes_keep(x)) return PXB_E_INVAL;
+  if (out_row != parent) memcpy(out_row, parent, (size_t)script_stride(cfg->n_proposers, N, depth));
+  uint8_t* const links = out_row + script_links_off(N);
+  for (uint32_t i = 0; i < 3u; ++i)
+    if (x.idx[i] != EXP_NO_SITE) links[x.idx[i]] = (uint8_t)explore_alt(x.links[x.idx[i]], x.dig[i], x.A);
+  return PXB_OK;
+}
 
 // an exploring call's arguments, whichever the family: device pointers in a
 // device form, host pointers in a host-buffer form
@@ -165,14 +183,13 @@ struct ExpArgs {
   uint32_t* counts;                 // (nullable, as status)
   uint32_t* status;
 };
-// the argument rules every exploring call shares; Space: pxb_explore_space or
-// pxb_explore_cover_space (what flag_mask may be is the family's rule)
-template <class Space>
-inline int explore_validate(const ExpArgs& a, const Space* sp, ExploreSpace* e) {
-  if (!sp) return PXB_E_INVAL;
-  if (int rc = validate_space_of(a.cfg, a.depth, sp->site_depth, sp->radius, e)) return rc;
+// the argument rules every exploring call shares, behind the rules of the
+// family's space (validate_space_of, and what the family adds); Space: the
+// call's space struct (what flag_mask may be is the family's rule)
+template <class X, class Space>
+inline int explore_validate(const ExpArgs& a, const Space* sp) {
   if ((a.count && !a.rows) || a.count > MAX_COUNT || !a.n_matches || (a.capacity && !a.ids)) return PXB_E_INVAL;
-  return (sp->flags & ~PXB_EXPLORE_MINIMAL) ? PXB_E_INVAL : PXB_OK;
+  return (sp->flags & ~X::FLAGS) ? PXB_E_INVAL : PXB_OK;
 }
 
 // the scratch of a device call over `total` candidates, from the stream-ordered
@@ -206,11 +223,13 @@ inline int explore_scratch(int dev, uint64_t total, hipStream_t st, ExpScratch* 
   return PXB_OK;
 }
 
-// behind a family's minimal kernel on st (which left the tiles' counts of the
-// listed bit `sel`): the list of the `total` candidates' flag bytes
-inline hipError_t explore_list_tail(uint64_t total, uint32_t sel, const ExpScratch& s, uint64_t first_g, uint64_t* d_ids,
-                                    uint64_t capacity, uint64_t* d_n_matches, hipStream_t st) {
-  hipError_t err = hipSuccess;
+// behind the candidate kernel on st: the minimal bits, counts and status, then the list
+template <class X>
+inline hipError_t explore_list(const ExpList<X>& l, const ExpScratch& s, uint64_t first_g, uint64_t* d_ids,
+                               uint64_t capacity, uint64_t* d_n_matches, hipStream_t st) {
+  hipLaunchKernelGGL(explore_minimal_kernel<X>, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, l);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
   size_t scan_b = s.scan_b;
   err = hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, scan_b, widen_iter(s.tcount, Widen{}), s.toff, (int64_t)s.ntiles, st);
   if (err != hipSuccess) return err;
@@ -218,75 +237,75 @@ inline hipError_t explore_list_tail(uint64_t total, uint32_t sel, const ExpScrat
                      s.list_base);
   if ((err = hipGetLastError()) != hipSuccess) return err;
   if (capacity) {
-    hipLaunchKernelGGL(explore_scatter_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, s.bytes, total, sel,
+    hipLaunchKernelGGL(explore_scatter_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, s.bytes, l.total, l.sel,
                        first_g, s.tcount, s.toff, s.list_base, d_ids, capacity);
     err = hipGetLastError();
   }
   return err;
 }
-// behind the candidate kernel on st: the minimal bits, counts and status, then the list
-inline hipError_t explore_list(const ExpList& l, const ExpScratch& s, uint64_t first_g, uint64_t* d_ids,
-                               uint64_t capacity, uint64_t* d_n_matches, hipStream_t st) {
-  hipLaunchKernelGGL(explore_minimal_kernel, dim3((unsigned)s.ntiles), dim3(XBLOCK), 0, st, l);
-  if (hipError_t err = hipGetLastError()) return err;
-  return explore_list_tail(l.total, l.sel, s, first_g, d_ids, capacity, d_n_matches, st);
-}
 
-inline hipError_t explore_no_hook(hipStream_t) { return hipSuccess; }
+// (a family with nothing around its candidate kernel)
+struct ExploreNoHooks {
+  bool aligned() const { return true; }
+  hipError_t before(hipStream_t) const { return hipSuccess; }
+  hipError_t after(hipStream_t) const { return hipSuccess; }
+};
 
-// The device form over validated arguments `a` on stream st: one call's bound
-// and the pointers' alignment (a family tests its own column's first), then
-// the counts zeroed | before(st) | fn(c) over the candidates | after(st) | the
-// minimal bits, counts, status and list, in this order on st.  `c`: the
-// candidate kernel's parameters with the family's own fields set; p, e, rows,
-// stride, total, depth, site_depth, flag_mask and bytes are set here.
-template <class Params, class Space, class Before, class After>
-int explore_device(const ExpArgs& a, const Space* sp, const ExploreSpace& e, hipStream_t st, void (*fn)(Params),
-                   Params& c, const Before& before, const After& after) {
-  if (a.count * e.T > MAX_CALL) return PXB_E_INVAL;                     // (count <= 2^30, T <= 2^30)
+// The device form over validated arguments `a` and the space `x` on stream st:
+// one call's bound and the pointers' alignment (hooks.aligned(): the family's
+// own column's), then the counts zeroed | hooks.before(st) | fn(c) over the
+// candidates | hooks.after(st) | the minimal bits, counts, status and list, in
+// this order on st.  `c`: the candidate kernel's parameters with the family's
+// own fields set; p, x, rows, stride, total, depth, site_depth, flag_mask and
+// bytes are set here.
+template <class X, class Params, class Space, class Hooks>
+int explore_device(const ExpArgs& a, const Space* sp, const typename X::Space& x, hipStream_t st, void (*fn)(Params),
+                   Params& c, const Hooks& hooks) {
+  const uint64_t T = X::total(x);
+  if (a.count * T > MAX_CALL) return PXB_E_INVAL;                       // (count <= 2^30, T <= 2^30)
   if (((uintptr_t)a.rows & 7u) || ((uintptr_t)a.ids & 7u) || ((uintptr_t)a.n_matches & 7u) ||
-      ((uintptr_t)a.counts & 3u) || ((uintptr_t)a.status & 3u))
+      ((uintptr_t)a.counts & 3u) || ((uintptr_t)a.status & 3u) || !hooks.aligned())
     return PXB_E_INVAL;
   int dev = 0;
   if (int rc = current_device(&dev)) return rc;
   if (a.count == 0) return PXB_OK;
 
-  const uint64_t total = a.count * e.T;
-  ExpScratch x;
-  if (int rc = explore_scratch(dev, total, st, &x)) return rc;
+  const uint64_t total = a.count * T;
+  ExpScratch s;
+  if (int rc = explore_scratch(dev, total, st, &s)) return rc;
 
   c.p = make_params(a.cfg);
   c.p.first_instance = 0;
-  c.e = e;
+  c.x = x;
   c.rows = a.rows;
   c.stride = script_stride(a.cfg->n_proposers, a.cfg->n_acceptors, a.depth);
   c.total = total;
   c.depth = a.depth;
   c.site_depth = sp->site_depth;
   c.flag_mask = sp->flag_mask;
-  c.bytes = x.bytes;
-  ExpList l{};
-  l.e = e;
+  c.bytes = s.bytes;
+  ExpList<X> l{};
+  l.x = x;
   l.rows = a.rows;
   l.stride = c.stride;
   l.total = total;
   l.P = a.cfg->n_proposers;
   l.sel = (sp->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
-  l.bytes = x.bytes;
-  l.tcount = x.tcount;
+  l.bytes = s.bytes;
+  l.tcount = s.tcount;
   l.counts = a.counts;
   l.status = a.status;
 
   hipError_t err = hipSuccess;
   do {
-    if (a.counts && (err = hipMemsetAsync(a.counts, 0, (size_t)(a.count * 12u * 4u), st)) != hipSuccess) break;
-    if ((err = before(st)) != hipSuccess) break;
+    if (a.counts && (err = hipMemsetAsync(a.counts, 0, (size_t)(a.count * X::CELLS * 3u * 4u), st)) != hipSuccess) break;
+    if ((err = hooks.before(st)) != hipSuccess) break;
     hipLaunchKernelGGL(fn, dim3((unsigned)((total + 63u) / 64u)), dim3(64), 0, st, c);
     if ((err = hipGetLastError()) != hipSuccess) break;
-    if ((err = after(st)) != hipSuccess) break;
-    err = explore_list(l, x, a.first_parent * e.T, a.ids, a.capacity, a.n_matches, st);
+    if ((err = hooks.after(st)) != hipSuccess) break;
+    err = explore_list(l, s, a.first_parent * T, a.ids, a.capacity, a.n_matches, st);
   } while (0);
-  const hipError_t f = hipFreeAsync(x.buf, st);   // (stream-ordered: after the launches above)
+  const hipError_t f = hipFreeAsync(s.buf, st);   // (stream-ordered: after the launches above)
   if (err == hipSuccess) err = f;
   return (err == hipSuccess) ? PXB_OK : hip_fail(err);
 }
@@ -297,10 +316,9 @@ int explore_device(const ExpArgs& a, const Space* sp, const ExploreSpace& e, hip
 // chunk's device arguments `d`.  `extra` (nullable), of extra_elem bytes a
 // parent (0: the family has none): the family's own per-parent output column.
 // An output the caller did not ask for reaches the device form as null.
-// T: the candidates of a parent; cnt_words: the words of a parent's counts.
-template <class Call>
-int explore_staged_over(const ExpArgs& h, uint64_t T, uint64_t cnt_words, void* extra, uint64_t extra_elem,
-                        const Call& call) {
+template <class X, class Call>
+int explore_staged(const ExpArgs& h, const typename X::Space& x, void* extra, uint64_t extra_elem, const Call& call) {
+  const uint64_t T = X::total(x), cnt_words = X::CELLS * 3u;
   if (device_count() == 0) return PXB_E_NODEV;
   *h.n_matches = 0;
   if (h.count == 0) return PXB_OK;
@@ -333,11 +351,5 @@ int explore_staged_over(const ExpArgs& h, uint64_t T, uint64_t cnt_words, void* 
   S.down(r_st, h.status, h.count);
   return S.finish();
 }
-// (the link-only families: T of the space, 4 x 3 counts a parent)
-template <class Call>
-int explore_staged(const ExpArgs& h, const ExploreSpace& e, void* extra, uint64_t extra_elem, const Call& call) {
-  return explore_staged_over(h, e.T, 12u, extra, extra_elem, call);
-}
-
 }  // namespace
 }  // namespace pxx

@@ -16,8 +16,9 @@
 // T_w = H T of them per parent.
 //
 // Here: the window space's sizes, unrank and rank, the window word a digit
-// stands for, the overwrite of a started lane's windows, and the two-axis
-// minimality test over the candidates' flag bytes.
+// stands for, the overwrite of a started lane's windows, the two-axis
+// minimality test over the candidates' flag bytes, and the joint space's policy
+// for the shared driver (ExploreWinX).
 #pragma once
 #include <stdint.h>
 
@@ -171,6 +172,41 @@ __host__ __device__ __forceinline__ bool explore_win_is_minimal(const ExploreWin
   }
   return !any;
 }
+
+// ---- the space policy of the joint space (explore_core.h: ExploreLinkX) ----
+// cw = h T + c; the cell is (r_w, r_l); the record holds a first per cell.
+struct ExploreWinX {
+  typedef ExploreWin Space;
+  typedef pxb_explore_win_reach Reach;
+  static constexpr uint32_t CELLS = EXW_CELLS;
+  static constexpr uint32_t COUNT_WORDS = CELLS * 32u, FIRST_WORDS = CELLS * 32u;
+  static constexpr uint32_t FLAGS = PXB_EXPLORE_MINIMAL | PXB_EXPLORE_WIN_OPEN;
+  __host__ __device__ static __forceinline__ uint64_t total(const Space& x) { return x.Tw; }
+  __host__ __device__ static __forceinline__ const ExploreSpace& links(const Space& x) { return x.e; }
+  __host__ __device__ static __forceinline__ ExploreSplit split(const Space& x, uint32_t g) {
+    const uint32_t tw = (uint32_t)x.Tw, tt = (uint32_t)x.e.T;
+    const uint32_t i = g / tw, cw = g - i * tw, h = cw / tt, c = cw - h * tt;
+    return ExploreSplit{i, cw, h, c};
+  }
+  __host__ __device__ static __forceinline__ uint32_t cell(const Space& x, uint32_t h, uint32_t c) {
+    return explore_win_cell(x, h, c);
+  }
+  __host__ __device__ static __forceinline__ bool is_minimal(const Space& x, uint32_t h, uint32_t c, const uint8_t* bytes) {
+    return explore_win_is_minimal(x, explore_win_unrank(x.w, h), explore_unrank(x.e, c), bytes);
+  }
+  __host__ __device__ static __forceinline__ uint32_t* count(Reach* o, uint32_t cell) {
+    return &o->count[0][0][0] + cell * 32u;
+  }
+  __host__ __device__ static __forceinline__ uint32_t* first(Reach* o, uint32_t cell) {
+    return &o->first[0][0][0] + cell * 32u;
+  }
+  // behind the begin: the windows of choice h
+  template <class Lane>
+  __host__ __device__ static __forceinline__ void apply(Lane& L, const Space& x, uint32_t h) {
+    explore_win_apply(L, x.w, explore_win_unrank(x.w, h));
+  }
+};
+static_assert(sizeof(pxb_explore_win_reach) == (ExploreWinX::COUNT_WORDS + ExploreWinX::FIRST_WORDS + 2u) * 4u, "Reach words");
 
 }  // namespace ev
 }  // namespace pxb

@@ -20,8 +20,9 @@
 //     the flag bytes: ascending g from the caller's cursor, below `capacity`.
 // Everything is sized from count x T: the device form never synchronises.  No
 // block waits for another; plain vector stores only.  All but the candidate
-// kernel, and the host side of both calls, live in explore_driver.h, which
-// pxb_explore_cover (paxos_explore_cover.hip) shares.
+// kernel, and the host side of both calls, live in explore_driver.h over the
+// link space's policy (explore_core.h: ExploreLinkX), which pxb_explore_cover
+// and pxb_explore_win share.
 //
 // Built as three units by proposer count (-DPXB_EXP_P=1|2|3) so that the slow
 // device compiles overlap; the unit of P = 1 also holds the other kernels and
@@ -46,7 +47,7 @@ namespace ev {
 
 struct ExpParams {
   EvParams p;
-  ExploreSpace e;
+  ExploreSpace x;
   const uint8_t* rows;              // the parents' rows
   uint64_t stride;
   uint64_t total;                   // candidates of this call (count * T <= 2^32)
@@ -70,9 +71,9 @@ __global__ __launch_bounds__(64) void paxos_explore_kernel(ExpParams k) {
   T.begin_count(1u, 0u);            // (an empty window: no records are counted)
   bool run = g < k.total;
   if (run) {
-    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
+    const uint32_t tt = (uint32_t)k.x.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
     const uint8_t* const row = k.rows + (uint64_t)i * k.stride;
-    const ExploreByte x = explore_byte(k.e, explore_unrank(k.e, c), row, N, k.site_depth, k.depth);
+    const ExploreByte x = explore_byte(k.x, explore_unrank(k.x, c), row, N, k.site_depth, k.depth);
     // a malformed parent runs nothing; a candidate that changes a keep site is skipped
     run = !explore_parent_bad(row, PM) && !explore_changes_keep(x);
     if (run) run = explore_begin(L, k.p, k.depth, row, x) == PXB_TRACE_OK;
@@ -108,7 +109,9 @@ namespace pxx {
 
 // explore_driver.h's rules and pxb_explore's own: an outcome condition; *fn: the shape's kernel
 static int validate(const ExpArgs& a, const pxb_explore_space* sp, ExploreSpace* e, exp_ptr* fn) {
-  if (int rc = explore_validate(a, sp, e)) return rc;
+  if (!sp) return PXB_E_INVAL;
+  if (int rc = validate_space_of(a.cfg, a.depth, sp->site_depth, sp->radius, e)) return rc;
+  if (int rc = explore_validate<ExploreLinkX>(a, sp)) return rc;
   if ((sp->flag_mask & 0xFFu) == 0u) return PXB_E_INVAL;
   *fn = lane_kernel<ExpFamily>(a.cfg);
   return *fn ? PXB_OK : PXB_E_INVAL;
@@ -130,14 +133,7 @@ int pxb_explore_row(const pxb_config* cfg, uint32_t depth, const pxb_explore_spa
   if (!space) return PXB_E_INVAL;
   if (int rc = validate_space_of(cfg, depth, space->site_depth, space->radius, &e)) return rc;
   if (!parent || !out_row || c >= e.T) return PXB_E_INVAL;
-  const uint32_t N = cfg->n_acceptors;
-  const ExploreByte x = explore_byte(e, explore_unrank(e, c), parent, N, space->site_depth, depth);
-  if (explore_changes_keep(x)) return PXB_E_INVAL;
-  if (out_row != parent) memcpy(out_row, parent, (size_t)script_stride(cfg->n_proposers, N, depth));
-  uint8_t* const links = out_row + script_links_off(N);
-  for (uint32_t i = 0; i < 3u; ++i)
-    if (x.idx[i] != EXP_NO_SITE) links[x.idx[i]] = (uint8_t)explore_alt(x.links[x.idx[i]], x.dig[i], x.A);
-  return PXB_OK;
+  return explore_row_links(cfg, depth, space->site_depth, e, parent, c, out_row);
 }
 
 int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t count, uint32_t depth,
@@ -149,7 +145,7 @@ int pxb_explore_device(const pxb_config* cfg, const uint8_t* d_rows, uint64_t co
   exp_ptr fn = nullptr;
   if (int rc = validate(a, space, &e, &fn)) return rc;
   ExpParams c{};
-  return explore_device(a, space, e, (hipStream_t)stream, fn, c, explore_no_hook, explore_no_hook);
+  return explore_device<ExploreLinkX>(a, space, e, (hipStream_t)stream, fn, c, ExploreNoHooks{});
 }
 
 int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
@@ -160,7 +156,7 @@ int pxb_explore(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint
   ExploreSpace e;
   exp_ptr fn = nullptr;
   if (int rc = validate(h, space, &e, &fn)) return rc;
-  return explore_staged(h, e, nullptr, 0, [&](const ExpArgs& d, void*) {
+  return explore_staged<ExploreLinkX>(h, e, nullptr, 0, [&](const ExpArgs& d, void*) {
     return pxb_explore_device(cfg, d.rows, d.count, depth, space, d.first_parent, d.ids, d.capacity, d.n_matches,
                               d.counts, d.status, nullptr);
   });

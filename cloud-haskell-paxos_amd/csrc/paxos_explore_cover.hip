@@ -9,24 +9,18 @@
 // entries, runs to its end folding its events into its mask in registers and
 // writes ONE flag byte (ran OK, held by §15's predicate).  No candidate row, no
 // event and no per-candidate mask is ever stored.  The wave then reduces into
-// the parents' reach records: a wave of 64 consecutive candidates can straddle
-// parents and radii, so it walks its distinct (parent, radius) keys as the
-// minimal kernel does, and per key the 29 classes as the cover kernel does: one
-// ballot, and where a lane has the class one atomic add to count[r][b] and one
-// atomic minimum to first[b] with the c of the lowest such lane (within one
-// parent c ascends with the lane).  Integer adds and minima only: the records
-// do not depend on the order the waves end in.  An init kernel in front sets
-// the records, a finishing kernel behind gives union_mask.  The list is
-// pxb_explore's (explore_driver.h, with the host side of both calls) over the
-// flag bytes.  No block waits for another; plain vector stores only.
+// the parents' reach records by its (parent, radius) keys: reach_reduce
+// (explore_reach.h, with the kernels that set and finish the records) over the
+// link space's policy (explore_core.h: ExploreLinkX; one first[b] a record).
+// The list, the device form and the host side are explore_driver.h's over the
+// same policy.  No block waits for another; plain vector stores only.
 //
 // Built as three units by proposer count (-DPXB_EXC_P=1|2|3); the unit of P = 1
 // also holds the other kernels and the entry points.
 #include <hip/hip_runtime.h>
-#include <string.h>
 
 #include "../../include/paxos_batch.h"
-#include "explore_cover_core.h"
+#include "explore_reach.h"
 #include "lane_shapes.h"
 #include "script_lane.h"
 
@@ -37,18 +31,11 @@
 namespace pxb {
 namespace ev {
 
-struct ExcParams {
-  EvParams p;
-  ExploreSpace e;
-  const uint8_t* rows;              // the parents' rows
-  uint64_t stride;
-  uint64_t total;                   // candidates of this call (count * T <= 2^32)
-  uint32_t depth, site_depth, flag_mask;
-  pxb_cover_query q;
-  uint8_t* bytes;                   // total flag bytes
-  pxb_explore_reach* reach;         // count records, initialised (nullable)
-};
+typedef ReachParams<ExploreLinkX> ExcParams;
 
+// (what the lane does around the run is spelled out here and in
+// paxos_explore_win_kernel, as in paxos_explore_kernel: shared, the same text
+// compiled to other register counts)
 template <int PM, int N, int W, bool LG = false>
 __global__ __launch_bounds__(64) void paxos_explore_cover_kernel(ExcParams k) {
   using SL = ScriptLane<PM, N, W, LG, LdsMem, ExploreEventDraws>;
@@ -67,9 +54,9 @@ __global__ __launch_bounds__(64) void paxos_explore_cover_kernel(ExcParams k) {
   E.begin();
   bool run = in;
   if (run) {
-    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
+    const uint32_t tt = (uint32_t)k.x.T, i = (uint32_t)g / tt, c = (uint32_t)g - i * tt;   // (g < 2^32)
     const uint8_t* const row = k.rows + (uint64_t)i * k.stride;
-    const ExploreByte x = explore_byte(k.e, explore_unrank(k.e, c), row, N, k.site_depth, k.depth);
+    const ExploreByte x = explore_byte(k.x, explore_unrank(k.x, c), row, N, k.site_depth, k.depth);
     // a malformed parent runs nothing; a candidate that changes a keep site is skipped
     run = !explore_parent_bad(row, PM) && !explore_changes_keep(x);
     if (run) run = explore_cover_begin(L, k.p, k.depth, row, x) == PXB_TRACE_OK;
@@ -85,33 +72,14 @@ __global__ __launch_bounds__(64) void paxos_explore_cover_kernel(ExcParams k) {
   }
   if (in) k.bytes[g] = (uint8_t)f;
   if (k.reach == nullptr) return;   // (wave-uniform)
-  // ---- the wave's reduction into the reach records ----
   uint32_t key = 0u, c = 0u;
   if (in) {
-    const uint32_t tt = (uint32_t)k.e.T, i = (uint32_t)g / tt;
+    const uint32_t tt = (uint32_t)k.x.T, i = (uint32_t)g / tt;
     c = (uint32_t)g - i * tt;
-    key = i * 4u + explore_radius(k.e, c);
+    key = i * 4u + explore_radius(k.x, c);
     if (c == 0u) k.reach[i].parent_mask = m;
   }
-  unsigned long long act = __ballot(m != 0u);
-  while (act != 0ull) {             // (wave-uniform) one distinct (parent, radius) a turn
-    const int lead = __ffsll(act) - 1;
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)key, lead);
-    const bool same = (m != 0u) & (key == k0);
-    pxb_explore_reach* const o = k.reach + (k0 >> 2);
-    uint32_t* const cnt = &o->count[0][0] + (k0 & 3u) * 32u;
-#pragma unroll 1
-    for (uint32_t b = 0; b < (uint32_t)PXB_COVER_CLASSES; ++b) {
-      const unsigned long long bal = __ballot(same & (((m >> b) & 1u) != 0u));
-      if (bal == 0ull) continue;    // (wave-uniform: no candidate of the key has the class)
-      const uint32_t cmin = (uint32_t)__builtin_amdgcn_readlane((int)c, __ffsll(bal) - 1);
-      if ((int)lane == lead) {
-        atomicAdd(cnt + b, (uint32_t)__popcll(bal));
-        atomicMin(&o->first[b], cmin);
-      }
-    }
-    act &= ~__ballot(same);
-  }
+  reach_reduce<ExploreLinkX>(k.reach, lane, m, key, c);
 }
 
 typedef void (*exc_ptr)(ExcParams);
@@ -130,32 +98,13 @@ PXB_LANE_UNIT(ExcFamily, PXB_EXC_P)
 
 namespace pxx {
 
-constexpr uint32_t REACH_WORDS = (uint32_t)(sizeof(pxb_explore_reach) / 4u);   // 128 counts | 32 firsts | 2 masks
-
-// one thread per word of the records: counts 0, firsts all-ones, masks 0
-__global__ __launch_bounds__(256) void reach_init_kernel(uint32_t* words, uint64_t n_words) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (t >= n_words) return;
-  const uint32_t w = (uint32_t)(t % REACH_WORDS);
-  words[t] = (w >= 128u && w < 160u) ? 0xFFFFFFFFu : 0u;
-}
-
-// behind the candidate kernel, 32 threads a parent, thread b: the union of the
-// counted classes (first[b] is all-ones where nothing was counted: only a count
-// comes with a minimum)
-__global__ __launch_bounds__(32) void reach_finish_kernel(pxb_explore_reach* reach) {
-  pxb_explore_reach* const o = reach + blockIdx.x;
-  const uint32_t b = threadIdx.x;
-  const bool has = (o->count[0][b] | o->count[1][b] | o->count[2][b] | o->count[3][b]) != 0u;
-  const unsigned long long bal = __ballot(has);
-  if (b == 0u) o->union_mask = (uint32_t)bal;
-}
-
 // explore_driver.h's rules and pxb_explore_cover's own: no outcome condition, or
 // one over the outcome bits; no reserved word; no production draws (the event
 // lanes have none); *fn: the shape's kernel
-static int validate(const ExpArgs& a, const pxb_explore_cover_space* sp, ExploreSpace* e, exc_ptr* fn) {
-  if (int rc = explore_validate(a, sp, e)) return rc;
+static int validate(const ExpArgs& a, const pxb_explore_cover_space* sp, ExploreSpace* e, ExcFamily::ptr* fn) {
+  if (!sp) return PXB_E_INVAL;
+  if (int rc = validate_space_of(a.cfg, a.depth, sp->site_depth, sp->radius, e)) return rc;
+  if (int rc = explore_validate<ExploreLinkX>(a, sp)) return rc;
   if ((sp->flag_mask != 0u && (sp->flag_mask & 0xFFu) == 0u) || sp->q.reserved != 0u) return PXB_E_INVAL;
   if (a.cfg->flags & PXB_CFG_TRACE_PRODUCTION) return PXB_E_INVAL;
   *fn = lane_kernel<ExcFamily>(a.cfg);
@@ -173,26 +122,12 @@ int pxb_explore_cover_device(const pxb_config* cfg, const uint8_t* d_rows, uint6
   using namespace pxx;
   const ExpArgs a{cfg, d_rows, count, depth, first_parent, d_ids, capacity, d_n_matches, d_counts, d_status};
   ExploreSpace e;
-  exc_ptr fn = nullptr;
+  ExcFamily::ptr fn = nullptr;
   if (int rc = validate(a, space, &e, &fn)) return rc;
-  if ((uintptr_t)d_reach & 7u) return PXB_E_INVAL;
   ExcParams c{};
   c.q = space->q;
   c.reach = d_reach;
-  // the records set in front of the candidates, union_mask behind them
-  const auto init = [&](hipStream_t st) {
-    if (!d_reach) return hipSuccess;
-    const uint64_t n_words = count * REACH_WORDS;
-    hipLaunchKernelGGL(reach_init_kernel, dim3((unsigned)((n_words + 255u) / 256u)), dim3(256), 0, st,
-                       reinterpret_cast<uint32_t*>(d_reach), n_words);
-    return hipGetLastError();
-  };
-  const auto finish = [&](hipStream_t st) {
-    if (!d_reach) return hipSuccess;
-    hipLaunchKernelGGL(reach_finish_kernel, dim3((unsigned)count), dim3(32), 0, st, d_reach);
-    return hipGetLastError();
-  };
-  return explore_device(a, space, e, (hipStream_t)stream, fn, c, init, finish);
+  return explore_device<ExploreLinkX>(a, space, e, (hipStream_t)stream, fn, c, ReachHooks<ExploreLinkX>{d_reach, count});
 }
 
 int pxb_explore_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
@@ -201,9 +136,9 @@ int pxb_explore_cover(const pxb_config* cfg, const uint8_t* rows, uint64_t count
   using namespace pxx;
   const ExpArgs h{cfg, rows, count, depth, 0, ids, capacity, n_matches, counts, status};
   ExploreSpace e;
-  exc_ptr fn = nullptr;
+  ExcFamily::ptr fn = nullptr;
   if (int rc = validate(h, space, &e, &fn)) return rc;
-  return explore_staged(h, e, reach, sizeof(pxb_explore_reach), [&](const ExpArgs& d, void* d_reach) {
+  return explore_staged<ExploreLinkX>(h, e, reach, sizeof(pxb_explore_reach), [&](const ExpArgs& d, void* d_reach) {
     return pxb_explore_cover_device(cfg, d.rows, d.count, depth, space, d.first_parent, d.ids, d.capacity,
                                     d.n_matches, d.counts, static_cast<pxb_explore_reach*>(d_reach), d.status,
                                     nullptr);

@@ -1795,8 +1795,8 @@ def _explore_two_call(call, nm, capacity):
     return ids[:min(nm.value, capacity)]
 
 
-def _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacity, d_counts, d_status):
-    """The checks the exploring device forms share."""
+def _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacity, d_counts, d_status, cnt_words=12):
+    """The checks the exploring device forms share (cnt_words: the words of a parent's counts)."""
     if d_n_matches is None:
         raise ValueError("d_n_matches is required")
     if capacity and d_ids is None:
@@ -1804,7 +1804,7 @@ def _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacit
     _check_script_call(cfg, d_rows, count, depth)
     _check_buf("d_n_matches", d_n_matches, 1, 8)
     _check_buf("d_ids", d_ids, capacity, 8)
-    _check_buf("d_counts", d_counts, 12 * count, 4)
+    _check_buf("d_counts", d_counts, cnt_words * count, 4)
     _check_buf("d_status", d_status, count, 4)
 
 
@@ -2275,15 +2275,7 @@ def explore_win_device(cfg: Config, d_rows, count: int, depth: int, site_depth: 
     (count, 3, 4, 3) and d_reach uint8 (count * 3080,) (8-byte aligned; after a
     synchronise, d_reach.cpu().numpy().view(win_reach_dtype()) gives the
     records).  Sizes and dtypes are checked here."""
-    if d_n_matches is None:
-        raise ValueError("d_n_matches is required")
-    if capacity and d_ids is None:
-        raise ValueError("d_ids is required when capacity > 0")
-    _check_script_call(cfg, d_rows, count, depth)
-    _check_buf("d_n_matches", d_n_matches, 1, 8)
-    _check_buf("d_ids", d_ids, capacity, 8)
-    _check_buf("d_counts", d_counts, 36 * count, 4)
-    _check_buf("d_status", d_status, count, 4)
+    _check_explore_device(cfg, d_rows, count, depth, d_n_matches, d_ids, capacity, d_counts, d_status, cnt_words=36)
     if d_reach is not None:
         _check_bytes("d_reach", d_reach, EXPLORE_WIN_REACH_BYTES * count)
     c = cfg.to_c(0, 1)

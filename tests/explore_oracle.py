@@ -27,7 +27,8 @@ OUT = os.path.join(HERE, "native", "_build", "libexplore_host.so")
 DEPS = [SRC, os.path.join(HERE, "native", "host_lane.h"), os.path.join(HERE, "native", "explore_host.h")] + [
     os.path.join(ROOT, "cloud-haskell-paxos_amd", "csrc", f)
     for f in ("paxos_ev.h", "paxos_ev_kernel.h", "paxos_device.h", "paxos_trace_core.h", "ev_layouts.h",
-              "lane_shapes.h", "script_core.h", "script_lane.h", "shrink_core.h", "explore_core.h")] + [
+              "lane_shapes.h", "script_core.h", "script_lane.h", "shrink_core.h", "explore_core.h",
+              "explore_cover_core.h", "cover_core.h", "events_core.h")] + [     # (explore_host.h includes the last three)
                   os.path.join(ROOT, "include", "paxos_batch.h")]
 RAN, HELD, MINIMAL = 1, 2, 4
 _lib = None

@@ -14,10 +14,7 @@
 #include <vector>
 
 #include "../../cloud-haskell-paxos_amd/csrc/explore_core.h"
-#include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
-#include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
 #include "explore_host.h"
-#include "host_lane.h"
 
 using namespace pxb;
 using namespace pxb::ev;
@@ -118,9 +115,8 @@ int explore_host_unrank(uint64_t S, uint32_t A, uint32_t R, const uint64_t* c, u
 int explore_host_run(const pxb_config* cfg, const uint8_t* rows, uint64_t count, uint32_t depth,
                      const pxb_explore_space* sp, uint64_t first_parent, uint64_t* ids, uint64_t capacity,
                      uint64_t* n_matches, uint32_t* counts, uint32_t* status, uint8_t* bytes) {
-  if (!cfg || !sp || !n_matches || (count && !rows) || depth > PXB_SCRIPT_MAX_DEPTH || sp->site_depth == 0u ||
-      sp->site_depth > depth || sp->radius > PXB_EXPLORE_MAX_RADIUS || !(sp->flag_mask & 0xFFu) ||
-      (sp->flags & ~PXB_EXPLORE_MINIMAL) || (capacity && !ids) || !trace_config_ok(cfg))
+  if (!explore_host_link_rules(cfg, depth, sp) || !n_matches || (count && !rows) || !(sp->flag_mask & 0xFFu) ||
+      (sp->flags & ~ExploreLinkX::FLAGS) || (capacity && !ids))
     return PXB_E_INVAL;
   const uint32_t P = cfg->n_proposers, N = cfg->n_acceptors;
   const ExploreSpace e = explore_space(explore_sites(P, N, sp->site_depth), cfg->delay_max, sp->radius);
@@ -135,7 +131,7 @@ int explore_host_run(const pxb_config* cfg, const uint8_t* rows, uint64_t count,
     for (uint64_t c = 0; c < e.T; ++c)
       if (int rc = dispatch(Cand{cfg, &e, row, depth, sp->site_depth, (uint32_t)c, sp->flag_mask, &f[(size_t)c]}))
         return rc;
-    explore_host_parent(e, P, row, i, sel, f.data(), out);
+    explore_host_parent<ExploreLinkX>(e, P, row, i, sel, f.data(), out);
   }
   *n_matches = pos;
   return 0;

@@ -2,7 +2,8 @@
 // (cloud-haskell-paxos_amd/csrc/explore_win_core.h: the window space, its unrank
 // and rank, the overwrite of a started lane's windows, the two-axis minimality
 // test; explore_cover_core.h: the lane and the flag byte) driven sequentially on
-// the host, one candidate at a time, so tests/test_explore_win_host.py can check
+// the host, one candidate at a time (explore_host.h, over the joint space's
+// policy), so tests/test_explore_win_host.py can check
 // it against brute force without a GPU.  The product runs the same code on the
 // device (paxos_explore_win.hip); the counts and the reach records here are the
 // plain sequential statement of what the kernels' wave reductions and atomics
@@ -16,9 +17,7 @@
 #include <vector>
 
 #include "../../cloud-haskell-paxos_amd/csrc/explore_win_core.h"
-#include "../../cloud-haskell-paxos_amd/csrc/lane_shapes.h"
-#include "../../cloud-haskell-paxos_amd/csrc/script_lane.h"
-#include "host_lane.h"
+#include "explore_host.h"
 
 using namespace pxb;
 using namespace pxb::ev;
@@ -29,64 +28,6 @@ static_assert(offsetof(pxb_explore_win_reach, first) == 1536 && offsetof(pxb_exp
               "record fields");
 
 namespace {
-
-// one candidate: what one lane of paxos_explore_win_kernel does before its wave's reduction
-struct Cand {
-  const pxb_config* cfg;
-  const ExploreWin* x;
-  const uint8_t* row;
-  uint32_t depth, site_depth, h, c, flag_mask;
-  const pxb_cover_query* q;
-  uint8_t* flags;
-  uint32_t* mask;
-};
-
-template <int PM, int N, int W, bool LG>
-int run_shape(const Cand& a) {
-  using Lane = typename ScriptLane<PM, N, W, LG, HostMem, ExploreEventDraws>::Lane;
-  constexpr uint32_t NL = 2u * PM * N;
-  *a.flags = 0u;
-  *a.mask = 0u;
-  const ExploreByte x = explore_byte(a.x->e, explore_unrank(a.x->e, a.c), a.row, N, a.site_depth, a.depth);
-  if (explore_parent_bad(a.row, PM) || explore_changes_keep(x)) return 0;
-  EvParams p = make_params(a.cfg);
-  p.first_instance = 0;
-  HostLane<Lane> H(p);
-  Lane& L = H.L;
-  L.e_acc = L.e_pin = false;
-  CoverLane<Lane> E;
-  E.begin();
-  const uint64_t guard_max = 100000ull * a.cfg->step_cap;   // a hang is a test failure
-  uint64_t guard = 0;
-  if (explore_cover_begin(L, p, a.depth, a.row, x) != PXB_TRACE_OK) return 0;
-  explore_win_apply(L, a.x->w, explore_win_unrank(a.x->w, a.h));
-  while (E.iter(L, p))
-    if (++guard > guard_max) return -100;
-  if (E.status != PXB_TRACE_OK) return 0;
-  uint16_t snt[NL];
-  script_sent(L, snt);
-  const uint32_t f = explore_cover_flags(E.res[3], E.mask, snt, NL, a.depth, a.flag_mask, *a.q);
-  *a.flags = (uint8_t)f;
-  *a.mask = (f & EXP_RAN) ? E.mask : 0u;
-  return 0;
-}
-
-#ifdef PXB_EXPLORE_WIN_HOST_MAIN
-// (the sanitizer build: one shape, P = 1, N = 3 on the 8-step wheel)
-int dispatch(const Cand& a) {
-  const pxb_config* c = a.cfg;
-  if (c->n_proposers != 1 || c->n_acceptors != 3 || wheel_for(c->delay_max) != 8 || c->n_ticks > 1) return -1;
-  return run_shape<1, 3, 8, false>(a);
-}
-#else
-// (the shapes of lane_shapes.h; -1: none)
-struct Run {
-  const Cand& a;
-  template <int PM, int N, int W, bool LG>
-  int run() const { return run_shape<PM, N, W, LG>(a); }
-};
-int dispatch(const Cand& a) { return host_lane_shape(a.cfg, Run{a}, -1); }
-#endif
 
 ExploreWin space_of(uint32_t P, uint32_t N, uint32_t delay_max, const pxb_explore_win_space* sp) {
   return explore_win_make(explore_space(explore_sites(P, N, sp->site_depth), delay_max, sp->radius),
@@ -153,57 +94,11 @@ int explore_win_host_run(const pxb_config* cfg, const uint8_t* rows, uint64_t co
                          const pxb_explore_win_space* sp, uint64_t first_parent, uint64_t* ids, uint64_t capacity,
                          uint64_t* n_matches, uint32_t* counts, pxb_explore_win_reach* reach, uint32_t* status,
                          uint8_t* bytes, uint32_t* masks) {
-  if (!cfg || !sp || !n_matches || (count && !rows) || depth > PXB_SCRIPT_MAX_DEPTH || sp->site_depth == 0u ||
-      sp->site_depth > depth || sp->radius > PXB_EXPLORE_MAX_RADIUS || (sp->flag_mask && !(sp->flag_mask & 0xFFu)) ||
-      (sp->flags & ~(PXB_EXPLORE_MINIMAL | PXB_EXPLORE_WIN_OPEN)) || sp->q.reserved || (capacity && !ids) ||
-      !trace_config_ok(cfg) || (cfg->flags & PXB_CFG_TRACE_PRODUCTION))
-    return PXB_E_INVAL;
-  const uint32_t P = cfg->n_proposers, N = cfg->n_acceptors;
-  const ExploreWin x = space_of(P, N, cfg->delay_max, sp);
-  if (!x.Tw || count * x.Tw > (1ull << 32)) return PXB_E_INVAL;
-  const uint64_t stride = script_stride(P, N, depth);
-  const uint32_t sel = (sp->flags & PXB_EXPLORE_MINIMAL) ? EXP_MINIMAL : EXP_HELD;
-  uint64_t pos = *n_matches;
-  std::vector<uint8_t> f((size_t)x.Tw);
-  std::vector<uint32_t> m((size_t)x.Tw);
-  for (uint64_t i = 0; i < count; ++i) {
-    const uint8_t* const row = rows + i * stride;
-    for (uint64_t cw = 0; cw < x.Tw; ++cw)
-      if (int rc = dispatch(Cand{cfg, &x, row, depth, sp->site_depth, (uint32_t)(cw / x.e.T), (uint32_t)(cw % x.e.T),
-                                 sp->flag_mask, &sp->q, &f[(size_t)cw], &m[(size_t)cw]}))
-        return rc;
-    // the minimal bits, the 12 x 3 counts and the list (the held bits are final before any minimal bit is set)
-    uint32_t cnt[EXW_CELLS * 3u] = {0u};
-    pxb_explore_win_reach r;
-    memset(&r, 0, sizeof r);
-    memset(r.first, 0xFF, sizeof r.first);
-    r.parent_mask = m[0];
-    for (uint64_t cw = 0; cw < x.Tw; ++cw) {
-      const uint64_t h = cw / x.e.T, c = cw % x.e.T;
-      const WinCand kw = explore_win_unrank(x.w, h);
-      const ExploreCand kl = explore_unrank(x.e, c);
-      uint8_t& fb = f[(size_t)cw];
-      if ((fb & EXP_HELD) && explore_win_is_minimal(x, kw, kl, f.data())) fb |= (uint8_t)EXP_MINIMAL;
-      for (uint32_t b = 0; b < 3u; ++b) cnt[(kw.r * 4u + kl.r) * 3u + b] += (fb >> b) & 1u;
-      if (fb & sel) {
-        if (pos < capacity) ids[pos] = (first_parent + i) * x.Tw + cw;
-        ++pos;
-      }
-      for (uint32_t b = 0; b < (uint32_t)PXB_COVER_CLASSES; ++b)
-        if ((m[(size_t)cw] >> b) & 1u) {
-          r.count[kw.r][kl.r][b] += 1u;
-          if ((uint32_t)cw < r.first[kw.r][kl.r][b]) r.first[kw.r][kl.r][b] = (uint32_t)cw;
-          r.union_mask |= 1u << b;
-        }
-    }
-    if (counts) memcpy(counts + i * EXW_CELLS * 3u, cnt, sizeof cnt);
-    if (status) status[i] = explore_parent_bad(row, P) ? PXB_SCRIPT_BAD : PXB_TRACE_OK;
-    if (bytes) memcpy(bytes + i * x.Tw, f.data(), (size_t)x.Tw);
-    if (reach) memcpy(reinterpret_cast<unsigned char*>(reach) + i * sizeof r, &r, sizeof r);
-    if (masks) memcpy(masks + i * x.Tw, m.data(), (size_t)x.Tw * 4u);
-  }
-  *n_matches = pos;
-  return 0;
+  if (!explore_host_link_rules(cfg, depth, sp)) return PXB_E_INVAL;
+  return explore_cover_host_run<ExploreWinX>(cfg, space_of(cfg->n_proposers, cfg->n_acceptors, cfg->delay_max, sp), rows,
+                                             count, depth, sp,
+                                             ExploreHostOut{first_parent, ids, capacity, nullptr, counts, status, bytes},
+                                             n_matches, reach, masks);
 }
 
 }  // extern "C"

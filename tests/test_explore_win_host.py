@@ -208,6 +208,29 @@ def test_minimal_is_joint():
     assert per_variant > link_only["n"]                                       # what the composed search lists again
 
 
+@pytest.mark.parametrize("all_mask", [0, XC.BIT["Q1_FOREIGN_ACCEPT"]])
+def test_no_window_radius_is_the_cover_build(all_mask):
+    """The link-only space is the joint space with one window choice: over a
+    grid of radius 0 (H = 1, r_w = 0) the host win build equals the host cover
+    build, on shape (b) at link radius 2 (T = 1,153), with the all-zero query and
+    with all = Q1_FOREIGN_ACCEPT."""
+    cfg, row, depth, sd, R, _, _ = XW.shape("b")
+    grid = pxb.WinGrid(0, 1, 1, radius=0)
+    assert pxb.explore_win_total(cfg, sd, R, grid) == pxb.explore_total(cfg, sd, R) == 1153
+    q = pxb.CoverQuery(all_mask=all_mask) if all_mask else None
+    w = XW.host_explore_win(cfg, row, depth, sd, R, grid, q, 0)
+    c = XC.host_explore_cover(cfg, row, depth, sd, R, q, 0)
+    assert np.array_equal(w["bytes"], c["bytes"]) and np.array_equal(w["ids"], c["ids"])
+    assert w["n"] == c["n"] and np.array_equal(w["status"], c["status"])
+    assert w["n"] > 0 and np.array_equal(w["masks"], c["masks"])
+    assert np.array_equal(w["counts"][:, 0], c["counts"]) and not w["counts"][:, 1:].any()
+    wr, cr = w["reach"], c["reach"]
+    assert np.array_equal(wr["count"][:, 0], cr["count"]) and not wr["count"][:, 1:].any()
+    assert np.array_equal(wr["first"][:, 0].min(axis=1), cr["first"]) and (wr["first"][:, 1:] == pxb.REACH_NONE).all()
+    assert np.array_equal(wr["parent_mask"], cr["parent_mask"]) and np.array_equal(wr["union_mask"], cr["union_mask"])
+    assert cr["union_mask"][0] != 0
+
+
 def test_five_parents_on_the_host():
     """A malformed parent, a parent with explicit windows and one with keep
     windows among good ones; first_parent; a capacity below the matches."""

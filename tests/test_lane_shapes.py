@@ -1,9 +1,9 @@
 """The lane-kernel families accept exactly the same shapes (csrc/lane_shapes.h):
 pxb_trace_instance, pxb_trace_batch_device, pxb_run_scripted_device,
 pxb_trace_scripted_device, pxb_shrink_batch_device, pxb_explore_device,
-pxb_trace_events_device, pxb_cover_device, pxb_explore_cover_device and
-pxb_shrink_cover_batch_device are called with an otherwise valid, empty job
-over a sweep of proposer counts, acceptor counts, delays and Tick counts.  A shape with a kernel passes
+pxb_trace_events_device, pxb_cover_device, pxb_explore_cover_device,
+pxb_explore_win_device and pxb_shrink_cover_batch_device are called with an
+otherwise valid, empty job over a sweep of proposer counts, acceptor counts, delays and Tick counts.  A shape with a kernel passes
 validation (PXB_E_NODEV without a GPU, PXB_OK with one), a shape without one is
 PXB_E_INVAL, and every family agrees with the table written out here."""
 import ctypes as C
@@ -41,6 +41,8 @@ def test_every_family_accepts_the_same_shapes():
     n_rec = C.c_uint32(0)
     sp = pxb.pxb_explore_space(1, 1, 0xFE, 0)
     csp = pxb.pxb_explore_cover_space(1, 1, 0xFE, 0, pxb.pxb_cover_query(0, 0, 0, 0))
+    wsp = pxb.pxb_explore_win_space(1, 1, 0xFE, 0, pxb.pxb_cover_query(0, 0, 0, 0), 1, 0, 1, 1)
+    win_device = pxb._win_fn("pxb_explore_win_device")
     pred = pxb.pxb_shrink_pred(0xFE, 8, (C.c_uint32 * 2)(0, 0), pxb.pxb_cover_query(0, 0, 0, 0))
     families = {
         "pxb_trace_instance": lambda c: L.pxb_trace_instance(c, 0, C.c_void_p(rec.ctypes.data), len(rec),
@@ -59,6 +61,8 @@ def test_every_family_accepts_the_same_shapes():
         "pxb_explore_cover_device": lambda c: L.pxb_explore_cover_device(c, None, 0, 1, C.byref(csp), 0, None, 0,
                                                                          C.c_void_p(nm.ctypes.data), None, None, None,
                                                                          None),
+        "pxb_explore_win_device": lambda c: win_device(c, None, 0, 1, C.byref(wsp), 0, None, 0,
+                                                       C.c_void_p(nm.ctypes.data), None, None, None, None),
         "pxb_shrink_cover_batch_device": lambda c: L.pxb_shrink_cover_batch_device(c, None, 0, 1, C.byref(pred), None,
                                                                                    None, None, None, None, None, None,
                                                                                    None),

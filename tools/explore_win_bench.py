@@ -158,10 +158,11 @@ def merge(path, prof_dir):
         "explore_cover_kernel_vgprs": int(cov[0]["VGPR_Count"]), "explore_cover_kernel_scratch": int(cov[0]["Scratch_Size"]),
         "win_over_cover_median": statistics.median(w_ms) / statistics.median(c_ms),
         "allowance_ms": allowance, "within_allowance": statistics.median(w_ms) <= allowance,
-        "explore_win_minimal_kernel_ms": ms(timed_runs("explore_win_minimal_kernel")[-1]),
-        "explore_minimal_kernel_ms": ms(timed_runs("explore_minimal_kernel")[-1]),
-        "win_reach_init_kernel_ms": ms(timed_runs("win_reach_init_kernel")[-1]),
-        "win_reach_finish_kernel_ms": ms(timed_runs("win_reach_finish_kernel")[-1])}
+        # (the minimal and record kernels are one template each: the joint space's instances)
+        "explore_win_minimal_kernel_ms": ms(timed_runs("explore_minimal_kernel<pxb::ev::ExploreWinX")[-1]),
+        "explore_minimal_kernel_ms": ms(timed_runs("explore_minimal_kernel<pxb::ev::ExploreLinkX")[-1]),
+        "win_reach_init_kernel_ms": ms(timed_runs("reach_init_kernel<384")[-1]),
+        "win_reach_finish_kernel_ms": ms(timed_runs("reach_finish_kernel<384")[-1])}
     with open(path, "w") as fh:
         json.dump(out, fh, indent=1)
         fh.write("\n")
